@@ -7,6 +7,8 @@
 A "step" is one full optimizer step (zero grads, forward, masked losses, backward, RCCL gradient
 all-reduce, diffGradNorm) of BASELINE.json's config C2 per GPU: base model, batch 8, 7x256x416
 synthetic image + sparse-radar batch, random-init weights.  Rank 0 prints ONE JSON line.
+
+    python bench.py ... --dump-outputs DIR                  # + what the last timed step computed, as DIR/<name>.npy
 """
 import argparse
 import json
@@ -284,8 +286,9 @@ def trace_frac(kernel, flops):
     return round(flops / (ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4) if ms > 0 else None
 
 
-def forward_only(model, batch, B, H, W, variant, reps=20):
-    """Eval-mode forward (forward-only roofline fraction), replayed from one HIP graph."""
+def forward_only(model, batch, B, H, W, variant, reps=20, outputs=None):
+    """Eval-mode forward (forward-only roofline fraction), replayed from one HIP graph.  outputs: a dict that
+    receives what the last timed replay computed (--dump-outputs)."""
     from camradepth_amd.inference import InferenceGraph
     ig = InferenceGraph(model, B, H, W)
     ig.run(batch["image"].cuda())
@@ -298,6 +301,14 @@ def forward_only(model, batch, B, H, W, variant, reps=20):
             ig.replay()
         e1.record()
     torch.cuda.synchronize()
+    if outputs is not None:
+        p = ig.plan
+        outputs.update(final_depth=p.out_depth[5].t.view(B, 1, H, W), half_depth=p.out_depth[4].t.view(B, 1, H // 2, W // 2),
+                       quarter_depth=p.out_depth[3].t.view(B, 1, H // 4, W // 4))
+        if p.seg_logits is not None:
+            outputs["final_seg"] = p.seg_out
+        if p.unsup_map is not None:
+            outputs["unsup_map"] = p.unsup_map
     model.train()
     ms = e0.elapsed_time(e1) / reps
     ips = B / (ms * 1e-3)
@@ -366,6 +377,36 @@ def cpu_baseline(variant, B_gpu=8, H=256, W=416, warm=2, timed_steps=5, budget_s
             "sample": f"fp32 CPU oracle, {variant}, 7x{H}x{W}: {warm} warm-up + up to {timed_steps} timed train steps (fwd+loss+bwd+diffGradNorm) "
                       f"at batch 2 and batch {B_gpu} [= value], 1 warm-up + up to 3 timed forward-only passes each (timed counts in "
                       f"timed_passes; cut only to stay inside {budget_s:.0f} s); {threads} torch threads on {cores} host CPUs"}
+
+
+# ---- --dump-outputs ------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 << 20            # all files of one dump together
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """Writes each entry of `arrays` (name -> tensor, array or list of numbers) as out_dir/<name>.npy: float64 if it is float64,
+    float32 otherwise.  Every entry gets an equal share of `budget`; a larger one is replaced by a fixed sample of its flattened
+    elements (sorted indices drawn from a RandomState seeded with DUMP_SEED: the same elements for the same size on every run),
+    so that two builds run with the same arguments can be compared file by file.  Returns {name: (shape, elements written)}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (budget - 256 * len(arrays)) // max(len(arrays), 1)      # (256: bound on the .npy header)
+    info = {}
+    for name, v in arrays.items():
+        t = v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        flat = t.reshape(-1)
+        cap = share // (8 if dt == torch.float64 else 4)
+        if flat.numel() > cap:
+            idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, flat.numel(), size=cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.to(dt).cpu().numpy()
+        else:
+            a = flat.to(dt).cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = (tuple(t.shape), a.size)
+    return info
 
 
 # ---- N ranks without a launcher ------------------------------------------------------------------------------------
@@ -483,8 +524,12 @@ def main():
                     help="A/B aid: crd_tune_pw_narrow(n) before the plans are built (0: the narrow streaming pointwise kernel off)")
     ap.add_argument("--tune-rege", type=int, default=None, choices=[0, 1],
                     help="A/B aid: crd_tune_igemm_reg_epilogue(n) (0: the LDS-staged epilogue for the 64 x 64 igemm tiles)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)      # tests: launcher contract on CPU (gloo)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "RANK" not in os.environ:       # no launcher: be the launcher (before any HIP call in this process)
         raise SystemExit(spawn_ranks(a.gpus, sys.argv[1:]))
     if a.stub:
@@ -522,7 +567,10 @@ def main():
     if a.inference:       # the reference's own "runtime" figure (Trainer.test(), runner.py:417-420), without its missing device sync
         batch = synth.make_batch(a.batch, a.height, a.width, seed=1234)
         scales = model.calibrate_fp8(batch["image"].cuda()) if a.fp8 else None
-        r = forward_only(model, batch, a.batch, a.height, a.width, a.variant, reps=max(a.steps, 10))
+        outputs = {} if a.dump_outputs else None
+        r = forward_only(model, batch, a.batch, a.height, a.width, a.variant, reps=a.steps, outputs=outputs)
+        if outputs:
+            dump_outputs(a.dump_outputs, outputs)
         line = {"metric": "inference frames/sec (eval forward, HIP graph)", "value": r["images_per_s"], "unit": "images/s",
                 "n_gpus": 1, "ms_per_forward": r["ms"], "higher_is_better": True, "dtype": "fp8" if a.fp8 else "bf16", "data": "synthetic",
                 "config": {"workload": f"CamRaDepth {a.variant} eval forward, {a.batch}x7x{a.height}x{a.width}"
@@ -568,6 +616,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     losses = ts.losses()
+    if a.dump_outputs and rank == 0:
+        # the last timed step's results, before the measurements below run the plan again: its loss terms, predictions,
+        # gradients and the parameters its optimizer step wrote
+        p = ts.plan
+        outputs = {"loss_terms": [losses[k] for k in ("loss", "full", "half", "quarter", "seg", "rmse")],
+                   "final_depth": p.out_depth[5].t.view(a.batch, 1, a.height, a.width),
+                   "half_depth": p.out_depth[4].t.view(a.batch, 1, a.height // 2, a.width // 2),
+                   "quarter_depth": p.out_depth[3].t.view(a.batch, 1, a.height // 4, a.width // 4)}
+        if p.seg_logits is not None:
+            outputs["final_seg"] = p.seg_out
+        outputs["grads"], outputs["params"] = model.flat_grad, model.flat
+        dump_outputs(a.dump_outputs, outputs)
     ms = 1e3 * dt / a.steps
     value = a.batch * world * a.steps / dt
 

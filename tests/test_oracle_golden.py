@@ -28,23 +28,39 @@ def test_param_inventory_matches_reference(variant):
         assert ref["num_params"] == 21966595 and len(mine) == 881
 
 
+def fp32_close(o32, g32, g64, tol):
+    """An fp32 oracle output against the reference's fp32 (g32) and fp64 (g64) runs of the same computation: within `tol` of g32,
+    or -- where the reference's own fp32 rounding is larger than that -- no further from the fp64 result than 8 times the reference's
+    fp32 output is.  How fp32 sums are grouped depends on the CPU's thread count and instruction set: the same oracle lies up to
+    5 times the reference's fp32 error from the fp64 result on the CPUs this was measured on (encoder maps of magnitude ~40: 3e-4)."""
+    return max_err(o32, g32) < tol or max_err(o32, g64) < 8 * max_err(g32, g64)
+
+
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_forward_eval_64x96(variant):
+    """The eval forward in fp64 against the reference's own fp64 run (tests/golden/make_fp64_golden.py): the two agree to the last
+    bits whatever CPU runs the test; and in fp32 against the reference's fp32 run (fp32_close)."""
     cfg = ModelConfig.variant(variant)
-    sd = golden_state_dict(cfg)
-    g = load_npz(f"forward64x96_{variant}.npz")
+    g, g64 = load_npz(f"forward64x96_{variant}.npz"), load_npz(f"forward64x96_fp64_{variant}.npz")
     batch = synth.make_batch(1, 64, 96, seed=1234)
-    taps = {}
+    taps, taps64 = {}, {}
     with torch.no_grad():
-        out = omodel.forward(sd, batch["image"], cfg, taps=taps)
+        out = omodel.forward(golden_state_dict(cfg), batch["image"], cfg, taps=taps)
+        out64 = omodel.forward({k: v.double() for k, v in golden_state_dict(cfg).items()}, batch["image"].double(), cfg, taps=taps64)
     for i in range(4):
-        assert max_err(taps[f"enc{i + 1}"].numpy(), g[f"eval_enc{i + 1}"]) < 1e-4
-    assert max_err(out["depth"]["final_depth"].numpy(), g["eval_final_depth"]) < TOL
-    assert max_err(out["depth"]["intermediate_depths"][3].numpy(), g["eval_depth_half"]) < TOL
-    assert max_err(out["depth"]["intermediate_depths"][2].numpy(), g["eval_depth_quarter"]) < TOL
+        k = f"eval_enc{i + 1}"
+        assert max_err(taps64[f"enc{i + 1}"].numpy(), g64[k]) < 1e-8, k
+        assert fp32_close(taps[f"enc{i + 1}"].numpy(), g[k], g64[k], 1e-4), k
+    for k, j in (("eval_final_depth", None), ("eval_depth_half", 3), ("eval_depth_quarter", 2)):
+        o64, o32 = ((o["depth"]["final_depth"] if j is None else o["depth"]["intermediate_depths"][j]).numpy() for o in (out64, out))
+        assert max_err(o64, g64[k]) < 1e-8, k
+        assert fp32_close(o32, g[k], g64[k], TOL), k
     if cfg.supervised_seg:
-        assert max_err(subsample(out["seg"]["final_seg"], 32768), g["eval_final_seg"]) < 1e-4
+        s64 = out64["seg"]["final_seg"].numpy().reshape(-1)
+        assert max_err(s64[::max(1, -(-s64.size // 32768))], g64["eval_final_seg"]) < 1e-7      # (subsample() rounds to fp32)
+        assert fp32_close(subsample(out["seg"]["final_seg"], 32768), g["eval_final_seg"], g64["eval_final_seg"], 1e-4)
     if cfg.unsupervised_seg:
+        assert np.array_equal(out64["seg"]["unsup_map"].numpy(), g64["eval_unsup_map"].astype(np.float32))
         assert np.array_equal(out["seg"]["unsup_map"].numpy(), g["eval_unsup_map"])
 
 
