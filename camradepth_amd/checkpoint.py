@@ -29,17 +29,47 @@ def load_state_dict_shape_match(model, checkpoint_state_dict):
     return missing, mismatched
 
 
+def trainstep_optimizer_state_dict(ts):
+    """A TrainStep's diffGradNorm state as the reference's optimizer.state_dict() (one param_group over the model's parameters in
+    their registration order).  `step` is the count of COMMITTED steps, read from the device: steps that skip_nonfinite skipped
+    are not in it, as GradScaler.step's skipped steps are not in the reference's."""
+    names = list(ts.model._names)
+    per = ts.optimizer_state()
+    lr, b1 = ts.schedule[min(ts.sched_steps, len(ts.schedule) - 1)] if ts.schedule else (ts.lr, ts.betas[0])
+    return {"state": {i: dict(per[n]) for i, n in enumerate(names)},
+            "param_groups": [{"lr": lr, "betas": (b1, ts.betas[1]), "eps": ts.eps, "weight_decay": ts.wd, "params": list(range(len(names)))}]}
+
+
+def load_trainstep_optimizer_state(ts, osd):
+    """The inverse of trainstep_optimizer_state_dict: moments, previous gradients, grad-norm averages and the step count."""
+    steps = {int(s["step"]) for s in osd["state"].values()}
+    if len(steps) != 1:
+        raise ValueError(f"load_trainstep_optimizer_state: non-uniform step counts {sorted(steps)}")
+    for i, n in enumerate(ts.model._names):
+        src = osd["state"][i]
+        a, b = ts.state.seg_host[i]
+        ts.m[a:b].copy_(torch.as_tensor(src["exp_avg"]).reshape(-1))
+        ts.v[a:b].copy_(torch.as_tensor(src["exp_avg_sq"]).reshape(-1))
+        ts.pg[a:b].copy_(torch.as_tensor(src["previous_grad"]).reshape(-1))
+        ts.egn[i] = float(src["exp_grad_norm"])
+    ts.step_count = steps.pop()
+    if ts.gate is not None:
+        ts.gate.zero_()
+        ts.gate[2] = ts.step_count
+
+
 def save_checkpoint(path, model, optimizer=None, steps=(0, 0)):
-    """Same dictionary as runner.py:369 (tensors moved to the CPU; the model itself stays on its device)."""
+    """Same dictionary as runner.py:369 (tensors moved to the CPU; the model itself stays on its device).  optimizer: a torch
+    optimizer (camradepth_amd.diffGradNorm) or a TrainStep (trainstep_optimizer_state_dict)."""
     state = {"state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "steps": list(steps)}
     if optimizer is not None:
-        osd = optimizer.state_dict()
+        osd = trainstep_optimizer_state_dict(optimizer) if hasattr(optimizer, "optimizer_state") else optimizer.state_dict()
         for st in osd["state"].values():
             for k, v in list(st.items()):
                 if torch.is_tensor(v):
                     st[k] = v.detach().cpu().clone()
         state["optimizer"] = osd
-        state["lr"] = optimizer.param_groups[0]["lr"]
+        state["lr"] = osd["param_groups"][0]["lr"] if hasattr(optimizer, "optimizer_state") else optimizer.param_groups[0]["lr"]
     torch.save(state, path)
     return state
 
@@ -55,5 +85,8 @@ def load_checkpoint(path_or_state, model, optimizer=None, shape_match=True):
         model.load_state_dict(strip_module_prefix(sd))
         missing, mismatched = [], []
     if optimizer is not None and "optimizer" in state:
-        optimizer.load_state_dict(state["optimizer"])
+        if hasattr(optimizer, "optimizer_state"):
+            load_trainstep_optimizer_state(optimizer, state["optimizer"])
+        else:
+            optimizer.load_state_dict(state["optimizer"])
     return missing, mismatched, state.get("steps", [0, 0])

@@ -31,36 +31,68 @@ void crd_register_nonfinite_flag(void* (*addr_of_flag)()) {
 }
 struct NfPtrs { int* p[NF_MAX]; };
 static __device__ int g_nf_any;
+static __device__ int g_nf_carry;     // what crd_nonfinite_capture took out of the flags and the host has not read yet
 __global__ __launch_bounds__(64) void k_nf_gather(NfPtrs ptrs, int n, int reset) {
   __shared__ int any;
-  if (threadIdx.x == 0) any = 0;
+  if (threadIdx.x == 0) any = g_nf_carry;
   __syncthreads();
   if ((int)threadIdx.x < n && *ptrs.p[threadIdx.x]) {
     any = 1;
     if (reset) *ptrs.p[threadIdx.x] = 0;
   }
   __syncthreads();
-  if (threadIdx.x == 0) g_nf_any = any;
+  if (threadIdx.x == 0) {
+    g_nf_any = any;
+    if (reset) g_nf_carry = 0;
+  }
 }
-extern "C" int crd_nonfinite_status(int32_t reset, crd_stream_t stream) {
-  // symbol addresses are per device: one resolved table per device ordinal
-  constexpr int MAX_DEV = 16;
-  static NfPtrs ptrs[MAX_DEV];
-  static int* any_addr[MAX_DEV];
-  static bool resolved[MAX_DEV];
-  if (g_nf_overflow) { crd_set_error("crd_nonfinite_status: more than %d translation units registered a flag", NF_MAX); return CRD_E_LAUNCH; }
+__global__ __launch_bounds__(64) void k_nf_capture(NfPtrs ptrs, int n, int* window_flag) {
+  __shared__ int any;
+  if (threadIdx.x == 0) any = 0;
+  __syncthreads();
+  if ((int)threadIdx.x < n && *ptrs.p[threadIdx.x]) {
+    any = 1;
+    *ptrs.p[threadIdx.x] = 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && any) {
+    g_nf_carry = 1;
+    if (window_flag) *window_flag = 1;
+  }
+}
+// symbol addresses are per device: one resolved table per device ordinal
+constexpr int NF_MAX_DEV = 16;
+static NfPtrs g_nf_ptrs[NF_MAX_DEV];
+static int* g_nf_any_addr[NF_MAX_DEV];
+static bool g_nf_resolved[NF_MAX_DEV];
+static int nf_resolve(const char* who) {          // -> device ordinal, or -1 with the error set
+  if (g_nf_overflow) { crd_set_error("%s: more than %d translation units registered a flag", who, NF_MAX); return -1; }
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) { crd_set_error("crd_nonfinite_status: no current device"); return CRD_E_LAUNCH; }
-  if (!resolved[dev]) {
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NF_MAX_DEV) { crd_set_error("%s: no current device", who); return -1; }
+  if (!g_nf_resolved[dev]) {
     for (int i = 0; i < g_nf_count; ++i) {
-      ptrs[dev].p[i] = reinterpret_cast<int*>(g_nf_addr_fns[i]());
-      if (!ptrs[dev].p[i]) { crd_set_error("crd_nonfinite_status: cannot resolve the device flag of translation unit %d", i); return CRD_E_LAUNCH; }
+      g_nf_ptrs[dev].p[i] = reinterpret_cast<int*>(g_nf_addr_fns[i]());
+      if (!g_nf_ptrs[dev].p[i]) { crd_set_error("%s: cannot resolve the device flag of translation unit %d", who, i); return -1; }
     }
     void* a = nullptr;
-    if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_nf_any)) != hipSuccess || !a) { crd_set_error("crd_nonfinite_status: cannot resolve the result word"); return CRD_E_LAUNCH; }
-    any_addr[dev] = reinterpret_cast<int*>(a);
-    resolved[dev] = true;
+    if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_nf_any)) != hipSuccess || !a) { crd_set_error("%s: cannot resolve the result word", who); return -1; }
+    g_nf_any_addr[dev] = reinterpret_cast<int*>(a);
+    g_nf_resolved[dev] = true;
   }
+  return dev;
+}
+extern "C" int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream) {
+  const int dev = nf_resolve("crd_nonfinite_capture");
+  if (dev < 0) return CRD_E_LAUNCH;
+  hipLaunchKernelGGL(k_nf_capture, dim3(1), dim3(64), 0, as_stream(stream), g_nf_ptrs[dev], g_nf_count, reinterpret_cast<int*>(window_flag));
+  if (hipGetLastError() != hipSuccess) { crd_set_error("crd_nonfinite_capture: launch failed"); return CRD_E_LAUNCH; }
+  return CRD_OK;
+}
+extern "C" int crd_nonfinite_status(int32_t reset, crd_stream_t stream) {
+  const int dev = nf_resolve("crd_nonfinite_status");
+  if (dev < 0) return CRD_E_LAUNCH;
+  NfPtrs* ptrs = g_nf_ptrs;
+  int** any_addr = g_nf_any_addr;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(k_nf_gather, dim3(1), dim3(64), 0, st, ptrs[dev], g_nf_count, reset ? 1 : 0);
   if (reset == 2) {                                 // clear only: asynchronous, nothing read back

@@ -161,9 +161,12 @@ constexpr int OPT_CHUNK = 4096;  // elements per workgroup
 
 // hp (device, optional): [beta1, beta2, eps, weight_decay, step_size] -- lets a captured HIP graph follow the
 // per-iteration OneCycleLR schedule without re-capture
+// GATED (skip_nonfinite): the same pass also tests every gradient element for NaN / inf and ORs the verdict into gate[0] -- one
+// word per accumulation window; an OR does not depend on the order of the workgroups.
+template <bool GATED>
 __global__ __launch_bounds__(TPB) void k_dgn_norm(const float* p, const float* g, const long long* seg_off, const int* blk2seg,
                                                   const int* blk2chunk, float wd, const float* hp, float* norm_sq,
-                                                  const unsigned char* active) {
+                                                  const unsigned char* active, int* gate) {
   if (hp) wd = hp[3];
   const int t = blk2seg[blockIdx.x];
   // A skipped tensor (`p.grad is None`, diffGradNorm.py:54-55) has NO gradient storage behind its segment when the gradients are used in
@@ -178,11 +181,14 @@ __global__ __launch_bounds__(TPB) void k_dgn_norm(const float* p, const float* g
   long long end = beg + OPT_CHUNK;
   if (end > seg_off[2 * t + 1]) end = seg_off[2 * t + 1];
   float s = 0.f;
+  bool bad = false;
   for (long long i = beg + threadIdx.x; i < end; i += TPB) {
     float gv = g[i];
+    if (GATED) bad |= !isfinite(gv);
     if (wd != 0.f) gv += wd * p[i];
     s += gv * gv;
   }
+  if (GATED && bad) atomicOr(gate, 1);                     // rare path
   s = wave_sum(s);
   __shared__ float sm[4];
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
@@ -194,9 +200,42 @@ __global__ __launch_bounds__(TPB) void k_dgn_norm(const float* p, const float* g
 // branch below sees the same norm on every run; e <- 0.95 e + 0.05 n ; factor = e > n ? e/(n+1e-8) : 1.
 // One wave per tensor.  The tensor's first workgroup is found by a 64-ary search in blk2seg (non-decreasing): two or
 // three dependent loads for the ~6000 workgroups of the model.
+// Gated commit (skip_nonfinite): gate = int32[8] on the device, [0] a gradient element was not finite (k_dgn_norm<true>), [1] a crd_sum_t
+// partial was dropped during the window's backward (crd_nonfinite_capture), [2] committed optimizer steps, [3] skipped steps, [4] the last
+// window's verdict, [5] the bits of this step's step_size.  The first wave of the scalar kernel takes the decision and keeps the
+// counters; the update kernel (launched behind it) only reads.  Bias corrections: the host's step_size (hp[4], or the argument) as long
+// as the device count of this step equals the host's (nothing skipped yet: the same bits as the ungated path), otherwise computed here in
+// fp64 from the fp64 copies of lr / beta1 / beta2 the host leaves in hp[8..13] (hp[14]: the host's step number as an int32).
+struct DgnGateHost { float step_size; int host_step; };
+__device__ __forceinline__ void dgn_gate_decide(int* gate, const float* hp, DgnGateHost h) {
+  const int bad = (gate[0] | gate[1]) ? 1 : 0;
+  gate[4] = bad;
+  if (bad) { gate[3] += 1; return; }
+  const int n = gate[2] + 1;
+  gate[2] = n;
+  float ss = h.step_size;
+  if (hp) {
+    ss = hp[4];
+    const int host_n = reinterpret_cast<const int*>(hp)[14];
+    if (n != host_n) {
+      const double* d = reinterpret_cast<const double*>(hp + 8);
+      const double bc1 = 1.0 - pow(d[1], (double)n), bc2 = 1.0 - pow(d[2], (double)n);
+      ss = (float)(d[0] * sqrt(bc2) / (bc1 + 1e-8));
+    }
+  }
+  gate[5] = __float_as_int(ss);
+}
+
+template <bool GATED>
 __global__ __launch_bounds__(256) void k_dgn_scalar(float* exp_grad_norm, const float* norm_part, float* factor, const unsigned char* active,
-                                                    int n, const long long* seg_off, const int* blk2seg, int n_blocks) {
+                                                    int n, const long long* seg_off, const int* blk2seg, int n_blocks, int* gate,
+                                                    const float* hp, DgnGateHost gh) {
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (GATED) {
+    const bool bad = gate[0] | gate[1];                    // (dgn_gate_decide does not write these two words)
+    if (blockIdx.x == 0 && threadIdx.x == 0) dgn_gate_decide(gate, hp, gh);
+    if (bad) return;                                       // skipped step: exp_grad_norm and factor stay as they are
+  }
   if (t >= n) return;
   if (active && !active[t]) { if (lane == 0) factor[t] = 1.f; return; }
   int lo = 0, len = n_blocks;                      // the first workgroup of tensor t lies in [lo, lo + len]
@@ -222,11 +261,16 @@ __global__ __launch_bounds__(256) void k_dgn_scalar(float* exp_grad_norm, const 
   }
 }
 
+template <bool GATED>
 __global__ __launch_bounds__(TPB) void k_dgn_update(float* p, const float* g, float* m, float* v, float* pg, const float* factor,
                                                     const long long* seg_off, const int* blk2seg, const int* blk2chunk,
                                                     const unsigned char* active, float beta1, float beta2, float eps, float wd,
-                                                    float step_size, const float* hp) {
+                                                    float step_size, const float* hp, const int* gate) {
   if (hp) { beta1 = hp[0]; beta2 = hp[1]; eps = hp[2]; wd = hp[3]; step_size = hp[4]; }
+  if (GATED) {
+    if (gate[4]) return;                                   // the window saw a non-finite gradient: nothing is written
+    step_size = __int_as_float(gate[5]);
+  }
   const int t = blk2seg[blockIdx.x];
   if (active && !active[t]) return;
   const long long beg = seg_off[2 * t] + (long long)blk2chunk[blockIdx.x] * OPT_CHUNK;
@@ -447,14 +491,46 @@ extern "C" int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, f
                 "crd_diffgradnorm_step: bad argument");
   hipStream_t st = as_stream(stream);
   const long long* so = reinterpret_cast<const long long*>(seg_off);
-  hipLaunchKernelGGL(k_dgn_norm, dim3(n_blocks), dim3(TPB), 0, st, p, g, so, blk2seg, blk2chunk, weight_decay, hp_dev, norm_sq, active);
-  hipLaunchKernelGGL(k_dgn_scalar, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so, blk2seg,
-                     n_blocks);
+  hipLaunchKernelGGL(k_dgn_norm<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, so, blk2seg, blk2chunk, weight_decay, hp_dev, norm_sq, active,
+                     nullptr);
+  hipLaunchKernelGGL(k_dgn_scalar<false>, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so,
+                     blk2seg, n_blocks, nullptr, nullptr, DgnGateHost{0.f, 0});
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
-  hipLaunchKernelGGL(k_dgn_update, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
-                     blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev);
+  hipLaunchKernelGGL(k_dgn_update<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
+                     blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr);
   CRD_LAUNCH_CHECK("crd_diffgradnorm_step");
+  return CRD_OK;
+}
+
+// ---- gated diffGradNorm (skip_nonfinite): include/camradepth_hip.h ----
+extern "C" int crd_diffgradnorm_norm_gated(const float* p, const float* g, float* norm_sq, const int64_t* seg_off, const int32_t* blk2seg,
+                                           const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active, float weight_decay,
+                                           const float* hp_dev, int32_t* gate, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && norm_sq && seg_off && blk2seg && blk2chunk && n_blocks > 0 && gate, "crd_diffgradnorm_norm_gated: bad argument");
+  hipLaunchKernelGGL(k_dgn_norm<true>, dim3(n_blocks), dim3(TPB), 0, as_stream(stream), p, g, reinterpret_cast<const long long*>(seg_off),
+                     blk2seg, blk2chunk, weight_decay, hp_dev, norm_sq, active, gate);
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_norm_gated");
+  return CRD_OK;
+}
+
+extern "C" int crd_diffgradnorm_commit_gated(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                             float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
+                                             const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                                             const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                             int32_t step, const float* hp_dev, int32_t* gate, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
+                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && gate,
+                "crd_diffgradnorm_commit_gated: bad argument");
+  hipStream_t st = as_stream(stream);
+  const long long* so = reinterpret_cast<const long long*>(seg_off);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
+  hipLaunchKernelGGL(k_dgn_scalar<true>, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so,
+                     blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step});
+  hipLaunchKernelGGL(k_dgn_update<true>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
+                     blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, gate);
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_commit_gated");
   return CRD_OK;
 }
 

@@ -65,7 +65,12 @@ class _Bridge(torch.autograd.Function):
                 plan.seg_grad_in.zero_()
             else:
                 plan.seg_grad_in.copy_(gouts[3])
+        gate = getattr(model, "_nf_gate", None)          # diffGradNorm(skip_nonfinite=True): the backward's dropped partials count
+        if gate is not None:
+            L.check(plan.lib.crd_nonfinite_capture(None, L.stream()), "crd_nonfinite_capture")
         plan.backward()
+        if gate is not None:
+            L.check(plan.lib.crd_nonfinite_capture(gate.data_ptr() + 4, L.stream()), "crd_nonfinite_capture")
         if model._grad_sync is not None:
             model._grad_sync.after_backward()
         return torch.zeros_like(model._anchor), None, None, None

@@ -13,7 +13,11 @@ _CHUNK = 4096
 
 
 class diffGradNorm(Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+    """skip_nonfinite=True: GradScaler.step's guard on the gated kernels -- a step whose gradients hold a NaN / inf element, or whose
+    backward dropped a non-finite partial from a fixed-point sum (camradepth_amd.CamRaDepth's backward), writes nothing and does
+    not advance any `step` count.  step() then reads the verdict once (one sync, as GradScaler.step does); found_inf holds it."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, skip_nonfinite=False):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: {}".format(lr))
         if not 0.0 <= eps:
@@ -24,6 +28,8 @@ class diffGradNorm(Optimizer):
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._groups = None
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.found_inf, self.skipped_steps = False, 0
 
     # ------------------------------------------------------------------ flat layout
     def _build(self, group):
@@ -70,6 +76,7 @@ class diffGradNorm(Optimizer):
         st["b2c"] = torch.tensor(b2c, dtype=torch.int32, device=dev)
         st["active"] = torch.ones(nt, dtype=torch.uint8, device=dev)
         st["step"] = 0
+        st["gate"] = None                        # skip_nonfinite: the verdict words (created on the first gated step)
         for t, (p, o) in enumerate(zip(ps, offs)):
             s = self.state[p]
             s["step"] = 0
@@ -121,9 +128,13 @@ class diffGradNorm(Optimizer):
                 gptr = fg.data_ptr()
                 st["active"].copy_(torch.tensor(act_host, dtype=torch.uint8))
                 st["act_host"] = None
-            st["step"] += 1
             beta1, beta2 = group["betas"]
             pbase = st["flat_p"].data_ptr() if st["flat_p"] is not None else st["base"]
+            if self.skip_nonfinite:
+                if not self._gated_step(lb, group, st, ps, pbase, gptr, act_host):
+                    self._mark_changed(ps)
+                continue
+            st["step"] += 1
             L.check(lb.crd_diffgradnorm_step(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
                                              st["egn"].data_ptr(), st["nsq"].data_ptr(), st["fac"].data_ptr(),
                                              st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps),
@@ -133,10 +144,49 @@ class diffGradNorm(Optimizer):
             for p, a_ in zip(ps, act_host):
                 if a_:
                     self.state[p]["step"] += 1
-            for ow in {getattr(p, "_crd_owner", None) for p in ps}:        # graph-replayed forwards re-pack their weights
-                if ow is not None and ow() is not None:
-                    ow().mark_params_changed()
+            self._mark_changed(ps)
         return loss
+
+    @staticmethod
+    def _mark_changed(ps):
+        for ow in {getattr(p, "_crd_owner", None) for p in ps}:        # graph-replayed forwards re-pack their weights
+            if ow is not None and ow() is not None:
+                ow().mark_params_changed()
+
+    def _gated_step(self, lb, group, st, ps, pbase, gptr, act_host):
+        """The gated launches of one group; -> True if the step was skipped."""
+        gate = self._gate(st, ps)
+        active = None if all(act_host) else st["active"].data_ptr()
+        beta1, beta2 = group["betas"]
+        L.check(lb.crd_diffgradnorm_norm_gated(pbase, gptr, st["nsq"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(),
+                                               st["b2c"].data_ptr(), st["nblk"], active, float(group["weight_decay"]), None,
+                                               gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
+        L.check(lb.crd_diffgradnorm_commit_gated(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
+                                                 st["egn"].data_ptr(), st["nsq"].data_ptr(), st["fac"].data_ptr(), st["seg"].data_ptr(),
+                                                 st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"], active,
+                                                 float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                                                 float(group["weight_decay"]), st["step"] + 1, None, gate.data_ptr(), L.stream()),
+                "crd_diffgradnorm_commit_gated")
+        skipped = bool(int(gate[4]))            # the one read of the step
+        gate[:2].zero_()                         # the next window starts without a verdict
+        self.found_inf = skipped
+        if skipped:
+            self.skipped_steps += 1
+            return True
+        st["step"] += 1
+        for p, a_ in zip(ps, act_host):
+            if a_:
+                self.state[p]["step"] += 1
+        return False
+
+    def _gate(self, st, ps):
+        """The group's verdict words; the owning model's backward captures its dropped partials into gate[1] (model._nf_gate)."""
+        if st["gate"] is None:
+            st["gate"] = torch.zeros(8, dtype=torch.int32, device=ps[0].device)
+            for ow in {getattr(p, "_crd_owner", None) for p in ps}:
+                if ow is not None and ow() is not None:
+                    ow()._nf_gate = st["gate"]
+        return st["gate"]
 
     def load_state_dict(self, state_dict):
         """Restores a checkpoint written by this class or by the reference's diffGradNorm (same per-parameter keys:

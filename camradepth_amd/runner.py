@@ -42,7 +42,7 @@ def unpack_batch(batch, input_channels):
 class Trainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, test_dataloader=None, learning_rate=6e-5, num_epochs=1,
                  update_interval=1, div_factor=2.0, max_depth=100.0, max_distances=(100.0, 50.0), num_classes=21, group=None,
-                 use_graph=True):
+                 use_graph=True, skip_nonfinite=False):
         if model.flat is None or not model.flat.is_cuda:
             raise L.CrdError("camradepth_amd.runner.Trainer needs the model on an MI355X (no CPU fallback)")
         self.model, self.cfg = model, model.cfg
@@ -50,6 +50,7 @@ class Trainer:
         self.learning_rate, self.num_epochs, self.update_interval, self.div_factor = learning_rate, num_epochs, update_interval, div_factor
         self.max_depth, self.max_distances, self.num_classes = max_depth, tuple(max_distances), num_classes
         self.group, self.use_graph = group, use_graph
+        self.skip_nonfinite = skip_nonfinite          # GradScaler.step's guard (runner.py:264): TrainStep(skip_nonfinite=...)
         self.criterion = {"depth": HL.MaskedSmoothL1Loss(), "seg": HL.MaskedFocalLoss()}      # runner.py:149
         self.step = None                     # the TrainStep of the batch shape seen last
         self._steps, self._train_state = {}, None     # (B, H, W) -> TrainStep, all sharing one TrainState
@@ -69,7 +70,8 @@ class Trainer:
             self.model.train()
             self._steps[key] = TrainStep(self.model, B, H, W, lr=self.learning_rate, update_interval=self.update_interval,
                                          schedule=one_cycle(max(steps, 2), self.learning_rate, div_factor=self.div_factor),
-                                         use_graph=self.use_graph, group=self.group, state=self._train_state)
+                                         use_graph=self.use_graph, group=self.group, state=self._train_state,
+                                         skip_nonfinite=self.skip_nonfinite)
             self._train_state = self._steps[key].state
         self.step = self._steps[key]
         return self.step

@@ -110,20 +110,23 @@ class TrainState:
         self.b2c = torch.tensor(b2c, dtype=torch.int32, device=dev)
         self.nt, self.nblk = nt, len(b2s)
         self.nsq = torch.zeros(self.nblk, device=dev)        # per-workgroup parts of ||g||^2 (summed in a fixed order)
-        self.hp = torch.zeros(8, device=dev)
-        self.hp_ring = [torch.zeros(8).pin_memory() for _ in range(64)]
+        # hyper-parameters of the next optimizer step: [0..4] read by every optimizer kernel, [8..14] by the gated one only (fp64 lr,
+        # beta1, beta2 and the host's step number: include/camradepth_hip.h, crd_diffgradnorm_commit_gated)
+        self.hp = torch.zeros(16, device=dev)
+        self.hp_ring = [torch.zeros(16).pin_memory() for _ in range(64)]
+        self.gate = None             # skip_nonfinite: int32[8] verdict words and step counters on the device (TrainStep._gate)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.update_interval = update_interval
         self.schedule = schedule
         self.iter_count = 0          # iterations (micro-batches) seen
         self.epoch_iter = 0          # ... in the current epoch (scheduler lag, runner.py:269)
         self.sched_steps = 0         # scheduler.step() calls so far = index into `schedule`
-        self.step_count = 0          # optimizer steps taken
+        self.step_count = 0          # optimizer steps taken (skip_nonfinite: attempted; the device counts the committed ones)
         self._window_open, self._window_pos = False, 0
 
 
 _STATE_FIELDS = ("m", "v", "pg", "egn", "fac", "seg", "b2s", "b2c", "nt", "nblk", "nsq", "hp", "hp_ring", "lr", "betas", "eps", "wd",
-                 "update_interval", "schedule", "iter_count", "epoch_iter", "sched_steps", "step_count", "_window_open", "_window_pos")
+                 "update_interval", "schedule", "iter_count", "epoch_iter", "sched_steps", "step_count", "_window_open", "_window_pos", "gate")
 
 
 class TrainStep:
@@ -133,14 +136,24 @@ class TrainStep:
     entry used by an optimizer step follows the reference's scheduler lag: `scheduler.step()` is only called from the
     (k+1)-th iteration of an epoch on (runner.py:269-270); start_epoch() marks the epoch boundary.  Parameters with
     requires_grad=False are frozen: no weight-gradient launch is recorded for them and the optimizer skips them
-    (diffGradNorm.py:54-55)."""
+    (diffGradNorm.py:54-55).
+
+    skip_nonfinite=True: GradScaler.step's guard (runner.py:264).  An accumulation window whose gradients hold a NaN / inf element,
+    or whose backward dropped a non-finite partial from a fixed-point sum, commits nothing: parameters and optimizer state stay
+    as they were, the schedule advances, training goes on.  The decision is taken on the device, after the whole backward, so
+    the optimizer of every bucket runs behind the last one (nothing is committed early); found_inf / skipped_steps read it."""
 
     def __init__(self, model, B, H, W, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, update_interval=1,
-                 use_graph=True, schedule=None, group=None, state=None):
+                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False):
         """state: the TrainState of another TrainStep of the same model (another batch shape of the same run) to continue;
         lr / betas / eps / weight_decay / update_interval / schedule are then taken from it."""
         assert model.training, "TrainStep drives the training path: call model.train() first"
         assert update_interval >= 1
+        if skip_nonfinite and getattr(model, "fp8_grad", False):
+            # delayed fp8 scaling records each backward's amax for the next one: a skipped window would leave a NaN amax behind
+            raise L.CrdError("TrainStep(skip_nonfinite=True) does not support fp8 data gradients (model.fp8_grad): a skipped step "
+                             "would poison the delayed scales")
+        self.skip_nonfinite = bool(skip_nonfinite)
         if state is not None and state.m.numel() != model.flat.numel():
             raise L.CrdError("TrainStep(state=...): the state belongs to a model with a different parameter count")
         self.state = state if state is not None else TrainState(model, lr, betas, eps, weight_decay, update_interval, schedule)
@@ -186,6 +199,35 @@ class TrainStep:
         self.use_graph = use_graph
         self.graphs = None
         self._zero, self._opt = True, True
+        if self.skip_nonfinite and self.state.gate is None:
+            self.state.gate = torch.zeros(8, dtype=torch.int32, device=self.dev)
+            self.state.gate[2] = self.state.step_count          # committed steps so far (a continued TrainState)
+
+    # ------------------------------------------------------------------ skip_nonfinite: what the device decided (one sync per read)
+    @property
+    def found_inf(self):
+        """True if the last closed accumulation window was skipped."""
+        return bool(self.gate is not None and int(self.gate[4]) != 0)
+
+    @property
+    def skipped_steps(self):
+        return 0 if self.gate is None else int(self.gate[3])
+
+    @property
+    def committed_steps(self):
+        """Optimizer steps that changed the parameters: the bias-correction count, and the per-parameter `step` of a checkpoint."""
+        return self.step_count if self.gate is None else int(self.gate[2])
+
+    def optimizer_state(self):
+        """diffGradNorm's state in the reference's per-parameter form (diffGradNorm.py:63-71), with `step` = committed steps: what
+        the reference's optimizer.state_dict() holds (runner.py:369).  Tensors are views of the device buffers."""
+        step = self.committed_steps
+        out = {}
+        for t, (name, (a, b)) in enumerate(zip(self.model._names, self.state.seg_host)):
+            shape = self.model._param(name).shape
+            out[name] = {"step": step, "exp_avg": self.m[a:b].view(shape), "exp_avg_sq": self.v[a:b].view(shape),
+                         "previous_grad": self.pg[a:b].view(shape), "exp_grad_norm": self.egn[t]}
+        return out
 
     def start_epoch(self):
         """Epoch boundary of the reference loop: the batch index restarts (scheduler lag) and pending accumulated
@@ -197,6 +239,8 @@ class TrainStep:
         p, st = self.plan, L.stream
         if self._zero:
             self.model.flat_grad.zero_()
+            if self.skip_nonfinite:
+                self.gate[:2].zero_()          # a new window: no verdict yet
         self.acc.zero_()
         p.forward(pack=False)                  # step() keeps the packed weights current (ensure_packed / _optimizer)
         for i, (j, key) in enumerate(((5, "full"), (4, "half"), (3, "quarter"))):
@@ -234,19 +278,57 @@ class TrainStep:
         lo, hi = (None, None) if key is None else self.sync.ranges[key]
         self.plan.pack(lo, hi)
 
+    # skip_nonfinite pieces: the flag captures around the backward, the gated norm (per bucket or all) and the gated commit
+    def _capture_flags(self, window):
+        L.check(self.lib.crd_nonfinite_capture(self.gate.data_ptr() + 4 if window else None, L.stream()), "crd_nonfinite_capture")
+
+    def _norm_gated(self, key=None):
+        m = self.model
+        b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
+        L.check(self.lib.crd_diffgradnorm_norm_gated(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.nsq.data_ptr() + 4 * b0,
+                                                     self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0, self.b2c.data_ptr() + 4 * b0, nb,
+                                                     None if mask is None else mask.data_ptr(), 0.0, self.hp.data_ptr(),
+                                                     self.gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
+
+    def _commit_gated(self):
+        """Every tensor's scalar and update, or none of them, then the re-pack of all weights (of unchanged ones after a skip: the
+        packed forms are a function of the fp32 parameters, so re-packing them writes the same bits)."""
+        m, mask = self.model, self.trainable_mask
+        L.check(self.lib.crd_diffgradnorm_commit_gated(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                       self.pg.data_ptr(), self.egn.data_ptr(), self.nsq.data_ptr(), self.fac.data_ptr(),
+                                                       self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(), self.nt, self.nblk,
+                                                       None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1,
+                                                       self.hp.data_ptr(), self.gate.data_ptr(), L.stream()),
+                "crd_diffgradnorm_commit_gated")
+        self.plan.pack()
+
     def _segments(self):
-        """The iteration as a list of (callable, bucket-to-launch-after | None | 'loss'), for the current
-        (self._zero, self._opt): zero the gradients first / all-reduce and run the optimizer last."""
+        """The iteration as a list of (callable, bucket-to-launch-after | None | 'loss' | 'gate'), for the current
+        (self._zero, self._opt): zero the gradients first / all-reduce and run the optimizer last.  skip_nonfinite: the backward is
+        bracketed by flag captures, then the gated norm ('gate': the ranks combine their verdicts here) and the gated commit."""
+        skip = getattr(self, "skip_nonfinite", False)
         segs = [(self._forward_and_loss_partials, "loss")]
         first = True
         for key in GradSync.ORDER:
             def run(key=key, first=first):
                 if first:
+                    if skip:
+                        self._capture_flags(False)     # what the forward's loss sums dropped is not the window's business
                     self._loss_backward()
                 self.plan.backward(tags=key)
+                if skip and not self.plan.split_late and getattr(self, "grad_hook", None) is not None:
+                    self.grad_hook(key)
             segs.append((run, key if self._opt else None))
             first = False
-        if self._opt:
+        if skip:
+            def tail(opt=self._opt):
+                self._capture_flags(True)
+                if opt:
+                    self._norm_gated()
+            segs.append((tail, "gate" if self._opt and self.dist_active else None))
+            if self._opt:
+                segs.append((self._commit_gated, None))
+        elif self._opt:
             segs.append((self._optimizer, None))
         return segs
 
@@ -261,7 +343,9 @@ class TrainStep:
         executes nothing; one eager warm-up iteration runs first (allocator, lazy module loading) and every buffer it
         changes is restored afterwards."""
         self.plan.ensure_packed()
-        saved = [t.clone() for t in (self.model.flat, self.m, self.v, self.pg, self.egn, self.nsq, self.fac, self.model.flat_grad)]
+        keep = (self.model.flat, self.m, self.v, self.pg, self.egn, self.nsq, self.fac, self.model.flat_grad) + \
+            ((self.gate,) if self.skip_nonfinite else ())
+        saved = [t.clone() for t in keep]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         self._zero, self._opt = True, True
@@ -283,7 +367,7 @@ class TrainStep:
             self._zero, self._opt = zero, opt
             self.graphs[(zero, opt)] = self._capture_variant()
         torch.cuda.synchronize()
-        for t, sv in zip((self.model.flat, self.m, self.v, self.pg, self.egn, self.nsq, self.fac, self.model.flat_grad), saved):
+        for t, sv in zip(keep, saved):
             t.copy_(sv)
         self.plan.packed_version = None        # the warm-up iteration packed ITS updated weights
 
@@ -296,9 +380,12 @@ class TrainStep:
             # (branches of ONE captured graph do not run concurrently on this stack; separate graphs on two streams do).
             # Multi-GPU: the loss all-reduce follows the first graph, and each bucket's gradient all-reduce is enqueued
             # behind its late graph (last iteration of an accumulation window only).
+            # skip_nonfinite: the late graphs and the per-bucket slices only run the gated norm (finiteness test included); the
+            # flag capture, the commit of every bucket and the re-pack follow the LAST bucket, on the main stream (tail graphs)
+            skip = self.skip_nonfinite
             segs = self._segments()
             main = torch.cuda.current_stream()
-            bsegs = segs[1:-1] if opt else segs[1:]
+            bsegs = segs[1:1 + len(GradSync.ORDER)]
             keys = list(GradSync.ORDER)
             g0 = None
             mains = []
@@ -319,8 +406,10 @@ class TrainStep:
                 self.late_stream.wait_stream(main)
                 with torch.cuda.graph(gl, stream=self.late_stream):
                     self.plan.run_late(key)
+                    if skip and getattr(self, "grad_hook", None) is not None:
+                        self.grad_hook(key)         # tests: runs (captured) where this bucket's gradients have become final
                     if opt and not self.dist_active:    # this bucket's gradients are final: its optimizer slice follows at once
-                        self._optimizer(key)
+                        self._norm_gated(key) if skip else self._optimizer(key)
                 gopt = None
                 if opt and self.dist_active:
                     # multi-GPU: the bucket's optimizer slice is a graph of its own, replayed on the late stream behind THAT
@@ -328,10 +417,23 @@ class TrainStep:
                     # backward and only the last bucket's slice is exposed
                     gopt = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gopt, stream=self.late_stream):
-                        self._optimizer(key)
+                        self._norm_gated(key) if skip else self._optimizer(key)
                 main.wait_stream(self.late_stream)
                 chain.append((g, gl, key, gopt))
-            return [(("late", g0, chain, None), None)]
+            tail = None
+            if skip:                                         # (the flag capture + commit, and -- multi-GPU -- the commit after the ranks agree)
+                gt = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gt):
+                    self._capture_flags(True)
+                    if opt and not self.dist_active:
+                        self._commit_gated()
+                gc = None
+                if opt and self.dist_active:
+                    gc = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gc):
+                        self._commit_gated()
+                tail = (gt, gc)
+            return [(("late", g0, chain, tail), None)]
         if not self.dist_active:      # no collective between the segments: the whole step is one graph (five fewer launches)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -386,8 +488,18 @@ class TrainStep:
         if probe is not None:
             e1.record(main)
             probe.append((e0, e1))
-        if go is not None:
+        if isinstance(go, tuple):              # skip_nonfinite: flag capture (+ commit); multi-GPU: the ranks agree, then the commit
+            go[0].replay()
+            if go[1] is not None:
+                self._agree()
+                go[1].replay()
+        elif go is not None:
             go.replay()
+
+    def _agree(self):
+        """Multi-GPU skip_nonfinite: every rank skips or commits together.  Non-finite gradient elements reach every rank through
+        the SUM all-reduce already; a rank's dropped fixed-point partials do not -- a MAX over the two verdict words spreads them."""
+        dist.all_reduce(self.gate[:2], op=dist.ReduceOp.MAX, group=self.sync.group)
 
     def set_batch(self, batch):
         self.plan.x_in.copy_(batch["image"], non_blocking=True)
@@ -417,7 +529,12 @@ class TrainStep:
             hp_host = self.hp_ring[self.step_count % len(self.hp_ring)]   # ring: the async copy may still be pending
             hp_host[0], hp_host[1], hp_host[2], hp_host[3] = b1, b2, self.eps, self.wd
             hp_host[4] = lr * math.sqrt(bc2) / (bc1 + 1e-8)
-            self.hp.copy_(hp_host, non_blocking=True)
+            if getattr(self, "skip_nonfinite", False):
+                hp_host.view(torch.float64)[4:7] = torch.tensor([lr, b1, b2], dtype=torch.float64)
+                hp_host.view(torch.int32)[14] = self.step_count
+                self.hp.copy_(hp_host, non_blocking=True)
+            else:
+                self.hp[:8].copy_(hp_host[:8], non_blocking=True)
         if self.use_graph and self.graphs is None:
             self._capture()
             self._zero, self._opt = zero, opt
@@ -438,6 +555,8 @@ class TrainStep:
             if after == "loss":
                 if self.dist_active:
                     dist.all_reduce(self.acc, group=self.sync.group)
+            elif after == "gate":
+                self._agree()
             elif after is not None and self.dist_active:
                 self.sync.launch(after)
                 if after == GradSync.ORDER[-1]:

@@ -56,9 +56,15 @@ typedef int64_t crd_sum_t;
  * TrainStep.losses(), the loss modules and camradepth_amd.lib.stat_checked() report NaN when it is set.  Sums whose TOTAL
  * leaves the range while every partial stays inside it still wrap (|statistic sum| > 8.8e12, |gradient sum| > 5.2e5). */
 int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
+/* Device-side capture of the same flags (skip_nonfinite): ONE 64-thread launch on `stream`, no host read, legal inside a captured
+ * graph.  ORs every translation unit's flag into a carry word and clears the flags; window_flag (optional, device int32) is ORed
+ * with the result as well.  crd_nonfinite_status() ORs the carry word into what it reports and clears it with the flags, so what
+ * the host sees is unchanged.  A training step calls it at the start of its backward (window_flag = NULL: what the forward's loss
+ * sums dropped does not count) and at the end (window_flag = the window's verdict word). */
+int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 6        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 7        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -620,6 +626,23 @@ int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, float* exp_a
                           const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
                           const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
                           int32_t step, const float* hp_dev, crd_stream_t stream);
+/* The same optimizer step split in two and GATED (skip_nonfinite, GradScaler.step semantics): nothing is written when the window saw a
+ * non-finite gradient.  gate: device int32[8], zeroed by the caller except for the counters: [0] a gradient element was NaN / inf (set
+ * by crd_diffgradnorm_norm_gated), [1] a crd_sum_t partial was dropped during the window's backward (crd_nonfinite_capture), [2]
+ * committed steps, [3] skipped steps, [4] the verdict of the last window (1 = skipped), [5] scratch (the step size in use).
+ * norm_gated: k_dgn_norm's pass over the blocks given (one bucket may be passed at a time: norm_sq / blk2seg / blk2chunk then point at
+ * that bucket's slice) plus the finiteness test.  commit_gated: the per-tensor scalars and the update over all blocks, or none.
+ * Bias corrections: `step` / lr / beta1 / beta2 when hp_dev is NULL (the host knows every verdict); with hp_dev, hp_dev[4] as long as
+ * the device count of this step equals the host's step number (int32 at hp_dev[14]), otherwise computed on the device in fp64 from
+ * the fp64 lr, beta1, beta2 at hp_dev[8..13].  hp_dev is then float[16]. */
+int crd_diffgradnorm_norm_gated(const float* p, const float* g, float* norm_sq, const int64_t* seg_off, const int32_t* blk2seg,
+                                const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active, float weight_decay,
+                                const float* hp_dev, int32_t* gate, crd_stream_t stream);
+int crd_diffgradnorm_commit_gated(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                  float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
+                                  const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                                  const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  int32_t step, const float* hp_dev, int32_t* gate, crd_stream_t stream);
 
 #ifdef __cplusplus
 }
