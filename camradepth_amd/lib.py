@@ -5,6 +5,7 @@ raises.  PyTorch is used only to own device memory and streams.
 """
 import ctypes as C
 import os
+import struct
 
 import torch
 
@@ -142,6 +143,8 @@ _SIGS = {
     "crd_resize_nearest_u8": "piiiipiip", "crd_resize_labels_nearest": "piiiipiip", "crd_seg_confusion": "ppiilppp",
     "crd_masked_l1_fwd": "pplpp", "crd_test_metrics": "ppilffpp", "crd_masked_l1_bwd": "pplppfpp", "crd_ce_fwd": "ppiilpp",
     "crd_ce_focal_bwd": "ppiilppfpp",
+    "crd_masked_dist_fwd": "pplpp", "crd_masked_dist_bwd": "pplppfipp", "crd_masked_berhu_max": "pplppp",
+    "crd_masked_berhu": "pplppLppfpp", "crd_smoothness_fwd": "ppiiiipp", "crd_smoothness_bwd": "ppiiiippfpp",
     "crd_diffgradnorm_step": "pppppppppppiipfffffipp",
     "crd_mlp_fused_supported": "iiii", "crd_mlp_fwd": "pp", "crd_mlp_reduce": "pipppiiipppp",
     "crd_nonfinite_status": "ip", "crd_nonfinite_capture": "pp",
@@ -192,6 +195,11 @@ def stat_checked(acc):
     if nonfinite(reset=False):
         v = torch.full_like(v, float("nan"))
     return v
+
+
+def f64_bits(x):
+    """IEEE-754 bit pattern of a double, for C ABI arguments declared uint64_t ..._f64_bits."""
+    return struct.unpack("<Q", struct.pack("<d", float(x)))[0]
 
 
 def check(rc, what=""):

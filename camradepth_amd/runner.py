@@ -14,7 +14,7 @@ from . import lib as L
 from . import losses as HL
 from .inference import InferenceGraph
 from .metrics import DepthMetrics, SegIoU
-from .trainer import TrainStep, one_cycle
+from .trainer import TrainStep, depth_criterion_mode, one_cycle
 
 
 def _nanmean(v):
@@ -42,7 +42,7 @@ def unpack_batch(batch, input_channels):
 class Trainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, test_dataloader=None, learning_rate=6e-5, num_epochs=1,
                  update_interval=1, div_factor=2.0, max_depth=100.0, max_distances=(100.0, 50.0), num_classes=21, group=None,
-                 use_graph=True, skip_nonfinite=False):
+                 use_graph=True, skip_nonfinite=False, criterion=None):
         if model.flat is None or not model.flat.is_cuda:
             raise L.CrdError("camradepth_amd.runner.Trainer needs the model on an MI355X (no CPU fallback)")
         self.model, self.cfg = model, model.cfg
@@ -51,7 +51,9 @@ class Trainer:
         self.max_depth, self.max_distances, self.num_classes = max_depth, tuple(max_distances), num_classes
         self.group, self.use_graph = group, use_graph
         self.skip_nonfinite = skip_nonfinite          # GradScaler.step's guard (runner.py:264): TrainStep(skip_nonfinite=...)
-        self.criterion = {"depth": HL.MaskedSmoothL1Loss(), "seg": HL.MaskedFocalLoss()}      # runner.py:149
+        # runner.py:149; criterion = another {"depth": ..., "seg": ...} of camradepth_amd.losses (TrainStep refuses what it cannot record)
+        self.criterion = criterion if criterion is not None else {"depth": HL.MaskedSmoothL1Loss(), "seg": HL.MaskedFocalLoss()}
+        depth_criterion_mode(self.criterion)
         self.step = None                     # the TrainStep of the batch shape seen last
         self._steps, self._train_state = {}, None     # (B, H, W) -> TrainStep, all sharing one TrainState
         self._infer = {}                     # (B, H, W) -> InferenceGraph
@@ -71,7 +73,7 @@ class Trainer:
             self._steps[key] = TrainStep(self.model, B, H, W, lr=self.learning_rate, update_interval=self.update_interval,
                                          schedule=one_cycle(max(steps, 2), self.learning_rate, div_factor=self.div_factor),
                                          use_graph=self.use_graph, group=self.group, state=self._train_state,
-                                         skip_nonfinite=self.skip_nonfinite)
+                                         skip_nonfinite=self.skip_nonfinite, criterion=self.criterion)
             self._train_state = self._steps[key].state
         self.step = self._steps[key]
         return self.step
@@ -105,7 +107,8 @@ class Trainer:
         return self._infer[key].run(image.cuda(non_blocking=True))
 
     def eval(self, epoch, save=False):
-        """-> (val_loss, RMSE): the mean final-depth SmoothL1 loss and the mean RMSE (x max_depth) over val_dataloader."""
+        """-> (val_loss, RMSE): the mean final-depth loss of self.criterion["depth"] and the mean RMSE (x max_depth) over
+        val_dataloader."""
         self.model.eval()
         L.nonfinite()          # ... and the other way round.  The loss modules report a dropped non-finite partial as NaN
         rows = []              # (lib.stat_checked), which the nanmean below leaves out exactly like the reference's np.nanmean (runner.py:320-347)

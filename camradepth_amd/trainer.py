@@ -25,6 +25,36 @@ from .optim import _CHUNK
 LOSS_W = (1.0, 1.0, 1.0, 0.2, 0.2)   # runner.py:213
 
 
+def depth_criterion_mode(criterion):
+    """criterion dict -> (depth mode, BerHu thresh) of the captured step, or CrdError.  The step records the kernels of the depth
+    criteria of camradepth_amd.losses that train (smooth-L1, Huber = smooth-L1 with beta 1, L1, RMSE, BerHu) and MaskedFocalLoss for
+    the segmentation; MaskedMSELoss is a detached metric, SmoothnessLoss takes an image, and other modules have no kernels here."""
+    from . import losses as HL
+    if criterion is None:
+        return "smooth_l1", None
+    if not isinstance(criterion, dict) or set(criterion) != {"depth", "seg"}:
+        raise L.CrdError("TrainStep(criterion=...) takes a dict {'depth': <loss>, 'seg': <loss>} of camradepth_amd.losses objects, got "
+                         f"{criterion!r}")
+    d, sg = criterion["depth"], criterion["seg"]
+    if type(sg) is not HL.MaskedFocalLoss:
+        raise L.CrdError(f"TrainStep(criterion=...): the seg criterion must be camradepth_amd.losses.MaskedFocalLoss, got {type(sg).__name__}")
+    modes = {HL.MaskedSmoothL1Loss: "smooth_l1", HL.MaskedHuberLoss: "smooth_l1", HL.MaskedL1Loss: "l1", HL.MaskedRMSELoss: "rmse",
+             HL.MaskedBerHuLoss: "berhu"}
+    mode = modes.get(type(d))
+    if mode is None:
+        raise L.CrdError(f"TrainStep(criterion=...): unsupported depth criterion {type(d).__name__}; the captured step supports "
+                         "MaskedSmoothL1Loss, MaskedHuberLoss, MaskedL1Loss, MaskedRMSELoss and MaskedBerHuLoss from camradepth_amd.losses")
+    thresh = None
+    if mode == "berhu":
+        try:
+            thresh = float(d.thresh)
+        except (TypeError, ValueError):
+            thresh = float("nan")
+        if not (thresh > 0.0 and math.isfinite(thresh)):
+            raise L.CrdError(f"TrainStep(criterion=...): MaskedBerHuLoss needs a finite thresh > 0, got {d.thresh!r}")
+    return mode, thresh
+
+
 def one_cycle(total_steps, max_lr, div_factor=2.0, pct_start=0.15, final_div_factor=1e4, base_m=0.85, max_m=0.95):
     """(lr, beta1) schedule of torch OneCycleLR(anneal='cos', cycle_momentum=True) as configured in runner.py:151-152."""
     initial, up_end = max_lr / div_factor, float(pct_start * total_steps) - 1
@@ -138,16 +168,21 @@ class TrainStep:
     requires_grad=False are frozen: no weight-gradient launch is recorded for them and the optimizer skips them
     (diffGradNorm.py:54-55).
 
+    criterion: {"depth": <loss>, "seg": MaskedFocalLoss()} of camradepth_amd.losses (runner.py:149; None = smooth-L1 + focal).  The
+    three depth levels record the chosen criterion's kernels; losses() reports its values.  BerHu's c is a function of the max |d|
+    over the GATHERED batch: the ranks reduce their maxima (MAX) at the loss point, with the sums, before any gradient is formed.
+
     skip_nonfinite=True: GradScaler.step's guard (runner.py:264).  An accumulation window whose gradients hold a NaN / inf element,
     or whose backward dropped a non-finite partial from a fixed-point sum, commits nothing: parameters and optimizer state stay
     as they were, the schedule advances, training goes on.  The decision is taken on the device, after the whole backward, so
     the optimizer of every bucket runs behind the last one (nothing is committed early); found_inf / skipped_steps read it."""
 
     def __init__(self, model, B, H, W, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, update_interval=1,
-                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False):
+                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False, criterion=None):
         """state: the TrainState of another TrainStep of the same model (another batch shape of the same run) to continue;
         lr / betas / eps / weight_decay / update_interval / schedule are then taken from it."""
         assert model.training, "TrainStep drives the training path: call model.train() first"
+        self._depth_mode, self._berhu_thresh = depth_criterion_mode(criterion)      # refused here, before anything is allocated
         assert update_interval >= 1
         if skip_nonfinite and getattr(model, "fp8_grad", False):
             # delayed fp8 scaling records each backward's amax for the next one: a skipped window would leave a NaN amax behind
@@ -179,6 +214,9 @@ class TrainStep:
                    "quarter": torch.zeros((B, 1, H // 4, W // 4), device=self.dev),
                    "seg": torch.zeros((B, H, W), dtype=torch.int64, device=self.dev)}
         self.acc = torch.zeros(16, dtype=L.SUM_DTYPE, device=self.dev)     # crd_sum_t: 4 x (sum, count, sum sq, -) for full/half/quarter/ce
+        if self._depth_mode == "berhu":
+            self.maxbits = torch.zeros(4, dtype=torch.int32, device=self.dev)     # per level: fp32 bits of max |d| (MAX-reduced)
+            self.berhu_acc = torch.zeros(8, dtype=L.SUM_DTYPE, device=self.dev)   # per level: (sum part1, sum part2 numerators)
         seg, b2s, nt = self.state.seg_host, self.state.b2s_host, self.state.nt
         trainable = torch.tensor([1 if model._param(n_).requires_grad else 0 for n_ in model._names], dtype=torch.uint8)
         self.frozen_names = [n_ for n_ in model._names if not model._param(n_).requires_grad]
@@ -235,6 +273,39 @@ class TrainStep:
         self.epoch_iter = 0
 
     # ------------------------------------------------------------------ pieces of one step
+    _depth_mode, _berhu_thresh = "smooth_l1", None      # (class defaults: the CPU control-flow tests build the object by hand)
+
+    def _depth_fwd(self, pred, tgt, i):
+        """Level i's loss partials into acc[4i:4i+3] = (sum, count, sum d^2) -- BerHu: (-, count, sum d^2) and maxbits[i]."""
+        a, mode = self.acc.data_ptr() + 32 * i, self._depth_mode
+        if mode == "smooth_l1":
+            L.check(self.lib.crd_masked_l1_fwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, L.stream()), "crd_masked_l1_fwd")
+        elif mode == "berhu":
+            L.check(self.lib.crd_masked_berhu_max(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, self.maxbits.data_ptr() + 4 * i,
+                                                  L.stream()), "crd_masked_berhu_max")
+        else:
+            L.check(self.lib.crd_masked_dist_fwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, L.stream()), "crd_masked_dist_fwd")
+
+    def _depth_bwd(self, pred, tgt, d, i, gmul):
+        a, mode = self.acc.data_ptr() + 32 * i, self._depth_mode
+        if mode == "smooth_l1":
+            L.check(self.lib.crd_masked_l1_bwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, None, gmul, d.data_ptr(), L.stream()),
+                    "crd_masked_l1_bwd")
+        elif mode == "berhu":                  # (the loss sums of phase b come with the gradient: losses() reads them)
+            L.check(self.lib.crd_masked_berhu(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, self.maxbits.data_ptr() + 4 * i,
+                                              L.f64_bits(self._berhu_thresh), self.berhu_acc.data_ptr() + 16 * i, None, gmul, d.data_ptr(),
+                                              L.stream()), "crd_masked_berhu")
+        else:
+            L.check(self.lib.crd_masked_dist_bwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, None, gmul,
+                                                 0 if mode == "l1" else 1, d.data_ptr(), L.stream()), "crd_masked_dist_bwd")
+
+    def _reduce_loss_partials(self):
+        """The loss point of a multi-GPU step (between the forward and the backward): the global sums and counts -- and BerHu's
+        global max |d| per level, which its c and therefore every gradient depend on."""
+        dist.all_reduce(self.acc, group=self.sync.group)
+        if self._depth_mode == "berhu":
+            dist.all_reduce(self.maxbits, op=dist.ReduceOp.MAX, group=self.sync.group)
+
     def _forward_and_loss_partials(self):
         p, st = self.plan, L.stream
         if self._zero:
@@ -242,11 +313,12 @@ class TrainStep:
             if self.skip_nonfinite:
                 self.gate[:2].zero_()          # a new window: no verdict yet
         self.acc.zero_()
+        if self._depth_mode == "berhu":
+            self.maxbits.zero_()
+            self.berhu_acc.zero_()
         p.forward(pack=False)                  # step() keeps the packed weights current (ensure_packed / _optimizer)
         for i, (j, key) in enumerate(((5, "full"), (4, "half"), (3, "quarter"))):
-            pred, tgt = p.out_depth[j].t, self.gt[key]
-            L.check(self.lib.crd_masked_l1_fwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), self.acc.data_ptr() + 32 * i, st()),
-                    "crd_masked_l1_fwd")
+            self._depth_fwd(p.out_depth[j].t, self.gt[key], i)
         if self.sup:
             L.check(self.lib.crd_ce_fwd(p.seg_out.data_ptr(), self.gt["seg"].data_ptr(), self.B, self.model.cfg.num_classes,
                                         self.H * self.W, self.acc.data_ptr() + 96, st()), "crd_ce_fwd")
@@ -255,9 +327,7 @@ class TrainStep:
         p, st = self.plan, L.stream
         scale = 1.0 / sum(LOSS_W) / self.update_interval
         for i, (j, key) in enumerate(((5, "full"), (4, "half"), (3, "quarter"))):
-            pred, tgt, d = p.out_depth[j].t, self.gt[key], p.out_depth[("grad", j)].t
-            L.check(self.lib.crd_masked_l1_bwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), self.acc.data_ptr() + 32 * i, None,
-                                               LOSS_W[i] * scale, d.data_ptr(), st()), "crd_masked_l1_bwd")
+            self._depth_bwd(p.out_depth[j].t, self.gt[key], p.out_depth[("grad", j)].t, i, LOSS_W[i] * scale)
         if self.sup:
             L.check(self.lib.crd_ce_focal_bwd(p.seg_out.data_ptr(), self.gt["seg"].data_ptr(), self.B, self.model.cfg.num_classes,
                                               self.H * self.W, self.acc.data_ptr() + 96, None, LOSS_W[3] * scale,
@@ -469,7 +539,7 @@ class TrainStep:
         main = self._current_stream()
         if g0 is not None:
             g0.replay()
-            dist.all_reduce(self.acc, group=self.sync.group)      # global loss denominators before the backward
+            self._reduce_loss_partials()       # global loss denominators (BerHu: and maxima) before the backward
         for gm, gl, key, gopt in chain:
             with trace.range("main:" + "+".join(key)):
                 gm.replay()
@@ -554,13 +624,15 @@ class TrainStep:
                     fns[i]()
             if after == "loss":
                 if self.dist_active:
-                    dist.all_reduce(self.acc, group=self.sync.group)
+                    self._reduce_loss_partials()
             elif after == "gate":
                 self._agree()
             elif after is not None and self.dist_active:
                 self.sync.launch(after)
                 if after == GradSync.ORDER[-1]:
                     self.sync.wait()
+        if self.dist_active and self._depth_mode == "berhu":
+            dist.all_reduce(self.berhu_acc, group=self.sync.group)     # BerHu's loss sums (phase b runs in the backward): losses() only
         if opt:                                # every bucket was re-packed behind its optimizer slice
             self.model.mark_params_changed()
             self.plan.packed_version = self.model._param_version
@@ -572,15 +644,28 @@ class TrainStep:
             self.sched_steps += 1
         return opt
 
+    def _level_losses(self, a):
+        """full / half / quarter values of the criterion from the host copy `a` of acc (BerHu: one more copy of its sums and maxima)."""
+        n = [a[4 * i + 1] for i in range(3)]
+        if self._depth_mode == "rmse":
+            return [float(torch.sqrt(a[4 * i + 2] / n[i])) for i in range(3)]
+        if self._depth_mode == "berhu":
+            from .losses import berhu_value
+            b = L.stat_value(self.berhu_acc.cpu())
+            mx = self.maxbits.cpu().view(torch.float32).double()
+            return [float(berhu_value(b[2 * i], b[2 * i + 1], n[i], mx[i], self._berhu_thresh)) for i in range(3)]
+        return [float(a[4 * i] / n[i]) for i in range(3)]         # smooth-L1 (Huber) / L1: sum / count
+
     def losses(self):
-        """Host view of the last iteration's loss terms (synchronises)."""
+        """Host view of the last iteration's loss terms (synchronises): the criterion's value per depth level; "rmse" is
+        sqrt(sum d^2 / count) of the full level whatever the criterion."""
         a = L.stat_value(self.acc.cpu())
         if L.nonfinite():
             # a NaN / infinite / out-of-range partial was dropped from a fixed-point sum since the last check (include/camradepth_hip.h:
             # crd_nonfinite_status): the sums are not what the reference would have computed -- it reports NaN here, so do we
             nan = float("nan")
             return {"loss": nan, "full": nan, "half": nan, "quarter": nan, "seg": nan, "rmse": nan}
-        full, half, quarter = (float(a[4 * i] / a[4 * i + 1]) for i in range(3))
+        full, half, quarter = self._level_losses(a)
         rmse = math.sqrt(float(a[2] / a[1]))
         seg = 0.0
         if self.sup:

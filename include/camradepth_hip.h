@@ -610,6 +610,42 @@ int crd_ce_fwd(const float* logits, const int64_t* labels, int32_t B, int32_t C,
 int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, const crd_sum_t* acc,
                      const float* gout, float gmul, float* dlogits, crd_stream_t stream);
 
+/* More depth criteria (loss_funcs.py:49-59,118-180; camradepth_amd/csrc/losses.hip).  MaskedHuberLoss (nn.HuberLoss, delta = 1) is
+ * smooth-L1 with beta = 1 and runs crd_masked_l1_fwd / _bwd.  d = pred - target over target > 0; crd_sum_t sums with
+ * CRD_STAT_FRAC_BITS, zeroed by the caller. */
+/* MaskedL1Loss / MaskedRMSELoss: acc[0] += sum |d|, acc[1] += #(target>0), acc[2] += sum d^2
+ * (L1 = acc0/acc1, RMSE = sqrt(acc2/acc1)) */
+int crd_masked_dist_fwd(const float* pred, const float* target, int64_t n, crd_sum_t* acc, crd_stream_t stream);
+/* mode 0 (L1):   dpred = gmul * gout[0] * sign(d) / acc[1]   (sign(0) = 0, as torch's abs backward)
+ * mode 1 (RMSE): dpred = gmul * gout[0] * d / (acc[1] * rmse)   (NaN on the mask when rmse = 0, as torch's sqrt backward)
+ * 0 where target <= 0; gout may be NULL = 1 */
+int crd_masked_dist_bwd(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const float* gout,
+                        float gmul, int32_t mode, float* dpred, crd_stream_t stream);
+/* MaskedBerHuLoss, phase (a): *maxbits = max(*maxbits, bits of max |d|) (the fp32 bit pattern of a non-negative value; an
+ * integer MAX all-reduce of it is the global max; caller zeroes it), acc[1] += #(target>0), acc[2] += sum d^2 (acc[0] untouched). */
+int crd_masked_berhu_max(const float* pred, const float* target, int64_t n, crd_sum_t* acc, int32_t* maxbits, crd_stream_t stream);
+/* MaskedBerHuLoss, phase (b), with c = thresh * (fp32 at maxbits) in fp64 (the global max after an all-reduce) and count = acc[1].
+ * thresh is a double passed as its IEEE-754 bit pattern (the reference's delta is an fp64 product; the C ABI's argument types are
+ * pointers, int32 / int64 / uint64 and float).  The reference's fp32 edges:
+ *   part1 = |d| if |d| < fp32(c) else 0,  part2 = |d|^2 / (2c) if fp32(|d|^2) - fp32(c^2) > 0 else 0  (F.threshold's strict
+ *   comparisons: |d| == c contributes nothing and gets no gradient);
+ * loss (optional, crd_sum_t[2]): loss[0] += sum part1, loss[1] += sum of part2's numerators; the loss is
+ *   (loss[0] + loss[1] / (2c)) / acc[1] -- NaN when c = 0 (all |d| equal to 0) or the mask is empty;
+ * dpred (optional) = gmul * gout[0] * sign(d) * (1 if |d| < c, |d| / c if part2 applies, else 0) / acc[1], 0 where target <= 0
+ * (zero everywhere when c = 0).  At least one of loss / dpred; thresh finite and > 0. */
+int crd_masked_berhu(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const int32_t* maxbits,
+                     uint64_t thresh_f64_bits, crd_sum_t* loss, const float* gout, float gmul, float* dpred, crd_stream_t stream);
+/* SmoothnessLoss: pred [B][1][H][W], image [B][C][H][W] fp32, H, W >= 2.  n = pred / (per-sample mean + 1e-7), edge weights
+ * exp(-mean_c |image difference|); acc crd_sum_t[B][3]: acc[b][0] += sum pred_b, acc[b][1] += sum over x-neighbours of
+ * w |n_j - n_j+1|, acc[b][2] += the same over y-neighbours (two launches).  loss = sum_b acc[b][1] / (B H (W-1)) +
+ * sum_b acc[b][2] / (B (H-1) W). */
+int crd_smoothness_fwd(const float* pred, const float* image, int32_t B, int32_t C, int32_t H, int32_t W, crd_sum_t* acc,
+                       crd_stream_t stream);
+/* dpred = gmul * gout[0] * dloss/dpred including the term through the per-sample mean (from the forward's acc; no reduction).  The
+ * image gets no gradient.  Under data parallelism gmul = local B / global B makes the denominators the gathered batch's. */
+int crd_smoothness_bwd(const float* pred, const float* image, int32_t B, int32_t C, int32_t H, int32_t W, const crd_sum_t* acc,
+                       const float* gout, float gmul, float* dpred, crd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * diffGradNorm.step (src/models/diffGradNorm.py:41-113) over flat fp32 buffers.
  * Tensor t occupies [seg_off[2t], seg_off[2t+1]) of every flat buffer (int64 pairs; gaps allowed).  Workgroup w processes chunk
