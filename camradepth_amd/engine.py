@@ -847,6 +847,8 @@ class Plan:
             if s > 0:
                 self.conv(grp, self.conv_desc(draw, ("dgrad", cw), src.C, k, stride, k // 2, src.H, src.W, d_enc_out[s - 1],
                                               gather=1), region=("dxs", s - 1, 0, src.C))
+            else:
+                enc0 = (grp, draw, cw)       # the input gradient's launch closes this group (_input_grad_op)
             self._push(grp)
             # per-stage scratch shared by all blocks of the stage
             hid = Cs * ratio
@@ -1105,7 +1107,45 @@ class Plan:
         head(5, "depth_activation_5", S[4], dS[4], 128 + n_extra, hmap)
         if self._defer is not None:
             self.flush_deferred(self.bwd_groups[dec_first_group])       # the first decoder group recorded = the last one executed
+        self._input_grad_op(enc0, dCB[4], dCBs1 if seg and cfg.supervised_seg else None, lay[4][0])
         self._finalise()
+
+    # x.grad (model._Bridge.backward when the input requires a gradient): ONE launch at the end of the enc0 segment, the last group of the
+    # backward pass, behind the patch embed's GroupNorm backward (which writes `draw`) and every decoder data gradient.  Recorded in every
+    # plan, live only while want_x_grad is True: with it off the pass is exactly the one without the feature.
+    X_GRAD_SLOT = 10                 # argument index of dx, set per backward by set_x_grad()
+
+    def _input_grad_op(self, enc0, dcb, dcb_seg, col0):
+        grp, draw, cw = enc0
+        B, H, W, Cin = self.B, self.H, self.W, self.cfg.input_channels
+        self.want_x_grad = False
+        self.x_grad_op = None
+        if cw.cout != 64 or Cin > 8:
+            return                   # outside the kernel (set_x_grad raises)
+        Hs, Ws = H // 4, W // 4
+        flops = 2.0 * B * Cin * 64 * (7 * Hs - 3) * (7 * Ws - 3)       # every (draw pixel, tap) pair that lands inside the image
+        io = nbytes(draw) + B * H * W * Cin * 2 * (2 if dcb_seg is not None else 1) + B * Cin * H * W * 4 + 64 * 49 * 8 * 2
+        op = Op(self.lib.crd_input_grad, [draw.t, _WPtr(cw, "w_fwd"), dcb.t, dcb_seg.t if dcb_seg is not None else None, dcb.ld, col0,
+                                          B, H, W, Cin, None], "crd_input_grad",
+                meta={"kernel": "k_input_grad", "flops": flops, "shape": f"input grad Cin{Cin} {H}x{W}"}, io=io, cond=("want_x_grad", True))
+        grp.append(op)
+        self.x_grad_op = op
+
+    def set_x_grad(self, dx):
+        """The next backward pass also writes d(loss)/d(x) into dx (fp32 [B, Cin, H, W], every element written); None turns it off."""
+        if dx is None:
+            self.want_x_grad = False
+            if self.x_grad_op is not None:
+                self.x_grad_op.args[self.X_GRAD_SLOT] = None      # no pointer to a tensor the caller may free outlives the pass
+            return
+        if self.x_grad_op is None:
+            raise L.CrdError("x.grad needs a 64-channel stage-0 patch embed and at most 8 input channels")
+        if self.fp8_grad:
+            raise L.CrdError("x.grad is not available with e4m3 data gradients (calibrate_fp8(..., grads=True)): the last decoder stage's "
+                             "x columns are e4m3 products there; recalibrate with grads=False")
+        assert dx.dtype == F32 and dx.is_contiguous() and tuple(dx.shape) == (self.B, self.cfg.input_channels, self.H, self.W)
+        self.x_grad_op.args[self.X_GRAD_SLOT] = dx.data_ptr()
+        self.want_x_grad = True
 
     def _stage_fwd_only(self, stage):
         """Run a decoder stage builder but drop its backward groups (branches without any loss)."""

@@ -34,7 +34,9 @@ class _Holder(nn.Module):
 
 class _Bridge(torch.autograd.Function):
     """Connects the HIP plan to torch.autograd: outputs are plain tensors, parameter gradients are
-    accumulated by the kernels straight into `param.grad` (views of one flat buffer)."""
+    accumulated by the kernels straight into `param.grad` (views of one flat buffer).  The input's gradient
+    (when x requires one) is a fresh fp32 tensor written by crd_input_grad at the end of the pass; the fp32 -> bf16
+    conversion of x (crd_nchw_to_pm) passes it straight through."""
 
     @staticmethod
     def forward(ctx, anchor, x, model, masks):
@@ -51,6 +53,7 @@ class _Bridge(torch.autograd.Function):
         return tuple(outs)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable          # no double backward: the kernels' gradients carry no graph
     def backward(ctx, *gouts):
         plan, model = ctx.plan, ctx.model
         model._ensure_grad_views()
@@ -65,15 +68,22 @@ class _Bridge(torch.autograd.Function):
                 plan.seg_grad_in.zero_()
             else:
                 plan.seg_grad_in.copy_(gouts[3])
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = torch.empty((plan.B, model.cfg.input_channels, plan.H, plan.W), dtype=torch.float32, device=plan.dev)
+            plan.set_x_grad(dx)
         gate = getattr(model, "_nf_gate", None)          # diffGradNorm(skip_nonfinite=True): the backward's dropped partials count
         if gate is not None:
             L.check(plan.lib.crd_nonfinite_capture(None, L.stream()), "crd_nonfinite_capture")
-        plan.backward()
+        try:
+            plan.backward()
+        finally:
+            plan.set_x_grad(None)
         if gate is not None:
             L.check(plan.lib.crd_nonfinite_capture(gate.data_ptr() + 4, L.stream()), "crd_nonfinite_capture")
         if model._grad_sync is not None:
             model._grad_sync.after_backward()
-        return torch.zeros_like(model._anchor), None, None, None
+        return torch.zeros_like(model._anchor), dx, None, None
 
 
 class CamRaDepth(nn.Module):

@@ -473,6 +473,21 @@ int crd_bicubic2x_bwd(const void* dy, int32_t dy_ld, int32_t dy_coff, int32_t B,
                       void* dx, int32_t dx_ld, int32_t dx_coff, int32_t accumulate, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradient with respect to the model input (x.grad).  For every input pixel, c < Cin (fp32 NCHW dx [B][Cin][H][W], every
+ * element written):
+ *   dx[b][c][iy][ix] = sum_{co < 64, ky, kx: oy = (iy + 3 - ky) / 4, ox = (ix + 3 - kx) / 4 exact and in range}
+ *                          draw[b][oy * W/4 + ox][co] * wpe[co][ky * 7 + kx][c]
+ *                    + dcb_depth[b][iy * W + ix][col0 + c] (+ dcb_seg[b][iy * W + ix][col0 + c] when dcb_seg is not NULL)
+ * i.e. the data gradient of the stage-0 patch embed (7x7, stride 4, pad 3, Cin -> 64) plus the x columns of the last decoder
+ * stages' concat gradients.  draw: bf16 pixel-major [B][H/4 * W/4][64]; wpe: the forward-packed bf16 weight [64][49][8]
+ * (channels >= Cin ignored); dcb_*: bf16 [B][H*W][dcb_ld], columns [col0, col0 + 8) read (those >= col0 + Cin ignored).
+ * 1 <= Cin <= 8 and H, W multiples of 4 (CRD_E_UNSUPPORTED otherwise); draw, wpe, dcb_* and dx 16-byte aligned, col0 and dcb_ld
+ * multiples of 8, col0 + 8 <= dcb_ld (CRD_E_INVALID).  No atomics: two identical calls give bit-identical dx.
+ * ------------------------------------------------------------------------------------------- */
+int crd_input_grad(const void* draw, const void* wpe, const void* dcb_depth, const void* dcb_seg, int32_t dcb_ld, int32_t col0,
+                   int32_t B, int32_t H, int32_t W, int32_t Cin, float* dx, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Layout / small elementwise helpers at the module boundary.
  * ------------------------------------------------------------------------------------------- */
 /* NCHW fp32 [B][C][H][W] -> pixel-major bf16 slice; channels C..Cpad-1 of the slice are zeroed. */
