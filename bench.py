@@ -9,6 +9,11 @@ all-reduce, diffGradNorm) of BASELINE.json's config C2 per GPU: base model, batc
 synthetic image + sparse-radar batch, random-init weights.  Rank 0 prints ONE JSON line.
 
     python bench.py ... --dump-outputs DIR                  # + what the last timed step computed, as DIR/<name>.npy
+    python bench.py ... --full                              # + every measurement the headline figure does not need
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line.  --full then also times each gradient
+bucket's all-reduce (N > 1), the per-kernel table and roofline, the floor budget, the step-time attribution, the eval forward and
+the CPU baseline, each after the timed steps; --no-roofline / --no-excess / --no-cpu-baseline leave parts of that out.
 """
 import argparse
 import json
@@ -509,9 +514,13 @@ def main():
                     help="config C4: transfer learning with the segmentation branch frozen (seg_* parameters requires_grad=False)")
     ap.add_argument("--update-interval", type=int, default=1, help="gradient accumulation (runner.py:218-222)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-excess", action="store_true", help="skip the warm-chain / chain-only / late-only attribution of the step time")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need (all-reduce per bucket, "
+                         "per-kernel table and roofline, floor budget, step-time attribution, eval forward, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel table, roofline and eval forward")
+    ap.add_argument("--no-excess", action="store_true",
+                    help="with --full: skip the warm-chain / chain-only / late-only attribution of the step time")
     ap.add_argument("--inference", action="store_true",
                     help="SURVEY 8f N4: eval-mode forward only, replayed from one HIP graph (e.g. --batch 1 --height 416 --width 800)")
     ap.add_argument("--fp8", action="store_true",
@@ -651,7 +660,7 @@ def main():
                                   "what": "main stream idle behind the late stream at the end of a step: last bucket's weight gradients"
                                           + (" + all-reduce" if ts.dist_active else "") + " + optimizer slice + re-pack"}
         ts.tail_probe = None
-    if ts.dist_active:          # the exchange step alone: each gradient bucket's SUM all-reduce, HIP events on the stream it runs on
+    if a.full and ts.dist_active:          # the exchange step alone: each gradient bucket's SUM all-reduce, HIP events on the stream it runs on
         from camradepth_amd.trainer import GradSync
         ar = {}
         for key in GradSync.ORDER:
@@ -671,7 +680,7 @@ def main():
     train_tflop_per_img = 3 * FWD_GFLOP[a.variant] * scale / 1e3
     out["mfma_frac_train_step"] = round(value / world * train_tflop_per_img / MFMA_BF16_PEAK_TFLOPS, 4)
 
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         agg = per_kernel_timing(ts)
         # the dominant kernel is a kernel TEMPLATE (all its tile instantiations together): k_conv3x3<*>, k_igemm<*>, ...
         # -- the 3x3 halo convolution is ONE family: the persistent kernel k_conv3x3p<...> and the two-workgroup kernel
@@ -712,18 +721,18 @@ def main():
             out["roofline"]["traffic_over_algorithmic"] = round(traffic / alg, 3)
         out["kernels"] = {k: {"launches": v[0], "ms_per_step": round(v[1], 3), "tflops": round(v[2] / (v[1] * 1e-3) / 1e12, 1)}
                           for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])}
-    if rank == 0:
+    if a.full and rank == 0:
         fb = floor_budget(ts.plan)
         out["floor_ms"], out["step_over_floor"], out["floor_budget"] = fb["floor_ms"], round(ms / fb["floor_ms"], 3), fb
-    if rank == 0 and world == 1 and not a.no_excess and not a.no_graph and "exposed_tail_us" in out and a.update_interval == 1:
+    if a.full and rank == 0 and world == 1 and not a.no_excess and not a.no_graph and "exposed_tail_us" in out and a.update_interval == 1:
         ex = excess_attribution(ts, ms, out["exposed_tail_us"]["median"] * 1e-3)
         if ex is not None:
             out["excess_ms"] = ex
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if a.full and rank == 0 and world == 1 and not a.no_roofline:
         out["forward_only"] = forward_only(model, batch, a.batch, a.height, a.width, a.variant)
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         small = a.height * a.width <= 256 * 416        # bounded: at larger frames only the batch-2-sized legs fit the time budget
         out["cpu_baseline"] = cpu_baseline(a.variant, a.batch if small else 1, a.height, a.width, timed_steps=5 if small else 2)
     if world > 1 or force_dist:

@@ -1,11 +1,12 @@
-# GPU box: kernel trace of the default bench command + one-step table; results under gpurun_out/prof_round/
+# GPU box: kernel trace of the bench command with its per-kernel timing pass (--full) + one-step table; results under the directory given as $1
 cd /tmp; export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-rm -rf gpurun_out/prof_round; mkdir -p gpurun_out/prof_round
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_round/trace -o bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-excess > gpurun_out/prof_round/bench.log 2>&1
-tail -1 gpurun_out/prof_round/bench.log
-db=$(ls gpurun_out/prof_round/trace/*.db | head -1)
-python3 tools/rocprof_summary.py "$db" gpurun_out/prof_round/kernel_stats.md > /dev/null
-python3 tools/rocprof_step.py "$db" > gpurun_out/prof_round/one_step.txt
-head -40 gpurun_out/prof_round/one_step.txt
-rm -rf gpurun_out/prof_round/trace
+O=${1:?usage: bash tools/profile_round.sh OUT_DIR}
+rm -rf $O; mkdir -p $O
+rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-excess > $O/bench.log 2>&1
+tail -1 $O/bench.log
+db=$(ls $O/trace/*.db | head -1)
+python3 tools/rocprof_summary.py "$db" $O/kernel_stats.md > /dev/null
+python3 tools/rocprof_step.py "$db" > $O/one_step.txt
+head -40 $O/one_step.txt
+rm -rf $O/trace
