@@ -163,10 +163,13 @@ constexpr int OPT_CHUNK = 4096;  // elements per workgroup
 // per-iteration OneCycleLR schedule without re-capture
 // GATED (skip_nonfinite): the same pass also tests every gradient element for NaN / inf and ORs the verdict into gate[0] -- one
 // word per accumulation window; an OR does not depend on the order of the workgroups.
-template <bool GATED>
+// CLIP (max_grad_norm): three more parts per workgroup, rows of norm_sq `ps` floats apart: [1] sum g^2 (the global norm's), and
+// with weight decay [2] sum g.p and [3] sum p^2, so that k_dgn_scalar can form ||c g + wd p||^2 once the coefficient c is known
+// without a second pass.  Row 0 stays the sum of (g + wd p)^2, the same operations in the same order as without CLIP.
+template <bool GATED, bool CLIP = false>
 __global__ __launch_bounds__(TPB) void k_dgn_norm(const float* p, const float* g, const long long* seg_off, const int* blk2seg,
                                                   const int* blk2chunk, float wd, const float* hp, float* norm_sq,
-                                                  const unsigned char* active, int* gate) {
+                                                  const unsigned char* active, int* gate, long long ps = 0) {
   if (hp) wd = hp[3];
   const int t = blk2seg[blockIdx.x];
   // A skipped tensor (`p.grad is None`, diffGradNorm.py:54-55) has NO gradient storage behind its segment when the gradients are used in
@@ -174,26 +177,85 @@ __global__ __launch_bounds__(TPB) void k_dgn_norm(const float* p, const float* g
   // segment walked past the end of that allocation -- a memory access fault whenever it was the last block of an allocator segment
   // (round 6: the full GPU suite hit it once; round 1-5's k_dgn_update already skipped such tensors, this kernel did not).
   if (active && !active[t]) {
-    if (threadIdx.x == 0) norm_sq[blockIdx.x] = 0.f;
+    if (threadIdx.x == 0) {
+      norm_sq[blockIdx.x] = 0.f;
+      if (CLIP) norm_sq[blockIdx.x + ps] = norm_sq[blockIdx.x + 2 * ps] = norm_sq[blockIdx.x + 3 * ps] = 0.f;
+    }
     return;
   }
   const long long beg = seg_off[2 * t] + (long long)blk2chunk[blockIdx.x] * OPT_CHUNK;
   long long end = beg + OPT_CHUNK;
   if (end > seg_off[2 * t + 1]) end = seg_off[2 * t + 1];
-  float s = 0.f;
+  float s = 0.f, sg = 0.f, sgp = 0.f, spp = 0.f;
   bool bad = false;
-  for (long long i = beg + threadIdx.x; i < end; i += TPB) {
-    float gv = g[i];
-    if (GATED) bad |= !isfinite(gv);
-    if (wd != 0.f) gv += wd * p[i];
-    s += gv * gv;
+  if (CLIP) {
+    // explicit fmaf: the contractions the compiler makes of the loop below (g + wd p, s + gv^2), which it no longer makes once the
+    // loop carries three more sums -- row 0 must keep the bits of norm_sq without CLIP
+    for (long long i = beg + threadIdx.x; i < end; i += TPB) {
+      float gv = g[i];
+      if (GATED) bad |= !isfinite(gv);
+      sg = fmaf(gv, gv, sg);
+      if (wd != 0.f) {
+        const float pv = p[i];
+        sgp = fmaf(gv, pv, sgp);
+        spp = fmaf(pv, pv, spp);
+        gv = fmaf(wd, pv, gv);
+      }
+      s = fmaf(gv, gv, s);
+    }
+  } else {
+    for (long long i = beg + threadIdx.x; i < end; i += TPB) {
+      float gv = g[i];
+      if (GATED) bad |= !isfinite(gv);
+      if (wd != 0.f) gv += wd * p[i];
+      s += gv * gv;
+    }
   }
   if (GATED && bad) atomicOr(gate, 1);                     // rare path
   s = wave_sum(s);
-  __shared__ float sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __shared__ float sm[4][4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) sm[0][w] = s;
+  if (CLIP) {
+    sg = wave_sum(sg); sgp = wave_sum(sgp); spp = wave_sum(spp);
+    if ((threadIdx.x & 63) == 0) { sm[1][w] = sg; sm[2][w] = sgp; sm[3][w] = spp; }
+  }
   __syncthreads();
-  if (threadIdx.x == 0) norm_sq[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];     // this workgroup's part (plain store)
+  if (threadIdx.x == 0) norm_sq[blockIdx.x] = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];     // this workgroup's part (plain store)
+  if (CLIP && threadIdx.x < 3) {
+    const int r = threadIdx.x + 1;
+    norm_sq[blockIdx.x + r * ps] = sm[r][0] + sm[r][1] + sm[r][2] + sm[r][3];
+  }
+}
+
+// max_grad_norm: torch.nn.utils.clip_grad_norm_'s total and coefficient from the sum g^2 parts of every workgroup (row 1 of
+// k_dgn_norm<., true>; frozen tensors wrote 0).  One workgroup adds them in a FIXED order with an fp64 accumulator (lane-strided,
+// then a tree in LDS): the same bits on every run, no float atomics.  clip[0] = total = ||g|| (fp32), clip[1] = coef =
+// min(1, max_norm / (total + 1e-6)) formed as torch forms it in fp32 (max_norm * reciprocal(total + 1e-6), then clamp(max=1):
+// a NaN total gives a NaN coefficient, as torch's with error_if_nonfinite=False).
+__global__ __launch_bounds__(256) void k_grad_norm_total(const float* sq, int n, float max_norm, float* clip) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)sq[i];
+  __shared__ double sm[256];
+  sm[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) sm[threadIdx.x] += sm[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float total = (float)sqrt(sm[0]);
+    float c = (1.f / (total + 1e-6f)) * max_norm;
+    if (c > 1.f) c = 1.f;
+    clip[0] = total;
+    clip[1] = c;
+  }
+}
+
+// c * g rounded on its own, as torch's in-place g.mul_(coef) leaves it, never fused with the weight-decay term that follows
+__device__ __forceinline__ float clip_mul(float g, float c) {
+#pragma clang fp contract(off)
+  return g * c;
 }
 
 // per tensor: ||g||^2 = its workgroups' parts added in a FIXED order (lane-strided, then the butterfly), so the e > n
@@ -226,10 +288,14 @@ __device__ __forceinline__ void dgn_gate_decide(int* gate, const float* hp, DgnG
   gate[5] = __float_as_int(ss);
 }
 
-template <bool GATED>
+// CLIP: the tensor's norm is that of c g + wd p, c = clip[1] (k_grad_norm_total).  With c == 1 it is row 0 of the parts, the
+// bits of the path without clipping; otherwise c^2 sum g^2 + 2 c wd sum g.p + wd^2 sum p^2 from rows 1-3, each row added in the
+// order row 0 is, combined in fp64.
+template <bool GATED, bool CLIP = false>
 __global__ __launch_bounds__(256) void k_dgn_scalar(float* exp_grad_norm, const float* norm_part, float* factor, const unsigned char* active,
                                                     int n, const long long* seg_off, const int* blk2seg, int n_blocks, int* gate,
-                                                    const float* hp, DgnGateHost gh) {
+                                                    const float* hp, DgnGateHost gh, float wd = 0.f, const float* clip = nullptr,
+                                                    long long ps = 0) {
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (GATED) {
     const bool bad = gate[0] | gate[1];                    // (dgn_gate_decide does not write these two words)
@@ -251,8 +317,23 @@ __global__ __launch_bounds__(256) void k_dgn_scalar(float* exp_grad_norm, const 
   }
   const int cnt = (int)((seg_off[2 * t + 1] - seg_off[2 * t] + OPT_CHUNK - 1) / OPT_CHUNK);
   float s = 0.f;
-  for (int i = lane; i < cnt; i += 64) s += norm_part[lo + i];
-  s = wave_sum(s);
+  const float c = CLIP ? clip[1] : 1.f;
+  if (!CLIP || c == 1.f) {
+    for (int i = lane; i < cnt; i += 64) s += norm_part[lo + i];
+    s = wave_sum(s);
+  } else {
+    if (hp) wd = hp[3];
+    float a = 0.f, b = 0.f, q = 0.f;
+    for (int i = lane; i < cnt; i += 64) {
+      a += norm_part[ps + lo + i];
+      b += norm_part[2 * ps + lo + i];
+      q += norm_part[3 * ps + lo + i];
+    }
+    a = wave_sum(a); b = wave_sum(b); q = wave_sum(q);
+    const double cd = c, wdd = wd;
+    s = (float)(cd * cd * a + 2.0 * cd * wdd * b + wdd * wdd * q);
+    if (s < 0.f) s = 0.f;                                  // rounding of a near-cancellation (a NaN stays NaN)
+  }
   if (lane == 0) {
     const float nrm = sqrtf(s);
     const float e = 0.95f * exp_grad_norm[t] + 0.05f * nrm;
@@ -261,11 +342,12 @@ __global__ __launch_bounds__(256) void k_dgn_scalar(float* exp_grad_norm, const 
   }
 }
 
-template <bool GATED>
+// CLIP: g <- c g (c = clip[1]) before the weight decay is added; c == 1 leaves every bit as it is
+template <bool GATED, bool CLIP = false>
 __global__ __launch_bounds__(TPB) void k_dgn_update(float* p, const float* g, float* m, float* v, float* pg, const float* factor,
                                                     const long long* seg_off, const int* blk2seg, const int* blk2chunk,
                                                     const unsigned char* active, float beta1, float beta2, float eps, float wd,
-                                                    float step_size, const float* hp, const int* gate) {
+                                                    float step_size, const float* hp, const int* gate, const float* clip = nullptr) {
   if (hp) { beta1 = hp[0]; beta2 = hp[1]; eps = hp[2]; wd = hp[3]; step_size = hp[4]; }
   if (GATED) {
     if (gate[4]) return;                                   // the window saw a non-finite gradient: nothing is written
@@ -277,10 +359,16 @@ __global__ __launch_bounds__(TPB) void k_dgn_update(float* p, const float* g, fl
   long long end = beg + OPT_CHUNK;
   if (end > seg_off[2 * t + 1]) end = seg_off[2 * t + 1];
   const float f = factor[t];
+  const float c = CLIP ? clip[1] : 1.f;
   for (long long i = beg + threadIdx.x; i < end; i += TPB) {
     float gv = g[i];
     const float pv = p[i];
-    if (wd != 0.f) gv += wd * pv;
+    if (CLIP) {                                            // (fmaf: the contraction of the line below, see k_dgn_norm)
+      gv = clip_mul(gv, c);
+      if (wd != 0.f) gv = fmaf(wd, pv, gv);
+    } else if (wd != 0.f) {
+      gv += wd * pv;
+    }
     const float g1 = gv * f;
     const float mv = beta1 * m[i] + (1.f - beta1) * g1;
     const float vv = beta2 * v[i] + (1.f - beta2) * gv * gv;
@@ -531,6 +619,53 @@ extern "C" int crd_diffgradnorm_commit_gated(float* p, const float* g, float* ex
   hipLaunchKernelGGL(k_dgn_update<true>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
                      blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, gate);
   CRD_LAUNCH_CHECK("crd_diffgradnorm_commit_gated");
+  return CRD_OK;
+}
+
+// ---- diffGradNorm with global gradient-norm clipping (max_grad_norm): include/camradepth_hip.h ----
+extern "C" int crd_diffgradnorm_norm_clip(const float* p, const float* g, float* parts, int64_t parts_stride, const int64_t* seg_off,
+                                          const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active,
+                                          float weight_decay, const float* hp_dev, int32_t* gate, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && parts && parts_stride >= n_blocks && seg_off && blk2seg && blk2chunk && n_blocks > 0,
+                "crd_diffgradnorm_norm_clip: bad argument");
+  const long long* so = reinterpret_cast<const long long*>(seg_off);
+  if (gate)
+    hipLaunchKernelGGL((k_dgn_norm<true, true>), dim3(n_blocks), dim3(TPB), 0, as_stream(stream), p, g, so, blk2seg, blk2chunk, weight_decay,
+                       hp_dev, parts, active, gate, (long long)parts_stride);
+  else
+    hipLaunchKernelGGL((k_dgn_norm<false, true>), dim3(n_blocks), dim3(TPB), 0, as_stream(stream), p, g, so, blk2seg, blk2chunk,
+                       weight_decay, hp_dev, parts, active, nullptr, (long long)parts_stride);
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_norm_clip");
+  return CRD_OK;
+}
+
+extern "C" int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                            float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
+                                            const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
+                                            int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
+                                            float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
+                                            int32_t* gate, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && parts && parts_stride >= n_blocks && factor && seg_off &&
+                    blk2seg && blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && max_norm > 0.f && clip,
+                "crd_diffgradnorm_commit_clip: bad argument");
+  hipStream_t st = as_stream(stream);
+  const long long* so = reinterpret_cast<const long long*>(seg_off);
+  const long long ps = parts_stride;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
+  hipLaunchKernelGGL(k_grad_norm_total, dim3(1), dim3(256), 0, st, parts + ps, n_blocks, max_norm, clip);
+  if (gate) {
+    hipLaunchKernelGGL((k_dgn_scalar<true, true>), dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, parts, factor, active, n_tensors,
+                       so, blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step}, weight_decay, (const float*)clip, ps);
+    hipLaunchKernelGGL((k_dgn_update<true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, (const float*)clip);
+  } else {
+    hipLaunchKernelGGL((k_dgn_scalar<false, true>), dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, parts, factor, active,
+                       n_tensors, so, blk2seg, n_blocks, nullptr, hp_dev, DgnGateHost{0.f, 0}, weight_decay, (const float*)clip, ps);
+    hipLaunchKernelGGL((k_dgn_update<false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, (const float*)clip);
+  }
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_commit_clip");
   return CRD_OK;
 }
 

@@ -90,7 +90,7 @@ class UnpackEntry(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 7          # include/camradepth_hip.h: CRD_ABI_VERSION
+ABI_VERSION = 8          # include/camradepth_hip.h: CRD_ABI_VERSION
 
 
 def load():
@@ -150,6 +150,7 @@ _SIGS = {
     "crd_mlp_fused_supported": "iiii", "crd_mlp_fwd": "pp", "crd_mlp_reduce": "pipppiiipppp",
     "crd_nonfinite_status": "ip", "crd_nonfinite_capture": "pp",
     "crd_diffgradnorm_norm_gated": "ppppppipfppp", "crd_diffgradnorm_commit_gated": "pppppppppppiipfffffippp",
+    "crd_diffgradnorm_norm_clip": "ppplpppipfppp", "crd_diffgradnorm_commit_clip": "ppppppplppppiipfffffipfppp",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "L": C.c_uint64, "f": C.c_float}
 EXPORTS = list(_SIGS)

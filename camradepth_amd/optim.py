@@ -12,12 +12,30 @@ from . import lib as L
 _CHUNK = 4096
 
 
+def check_max_grad_norm(value, who):
+    """None (no clipping) or a max_norm of torch.nn.utils.clip_grad_norm_ (> 0; +inf: the norm only) -> float | None, or CrdError."""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not v > 0.0:                                    # (NaN fails this too)
+        raise L.CrdError(f"{who}(max_grad_norm={value!r}): max_grad_norm must be a number > 0 (float('inf') monitors the norm only)")
+    return v
+
+
 class diffGradNorm(Optimizer):
     """skip_nonfinite=True: GradScaler.step's guard on the gated kernels -- a step whose gradients hold a NaN / inf element, or whose
     backward dropped a non-finite partial from a fixed-point sum (camradepth_amd.CamRaDepth's backward), writes nothing and does
-    not advance any `step` count.  step() then reads the verdict once (one sync, as GradScaler.step does); found_inf holds it."""
+    not advance any `step` count.  step() then reads the verdict once (one sync, as GradScaler.step does); found_inf holds it.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, skip_nonfinite=False):
+    max_grad_norm=c: torch.nn.utils.clip_grad_norm_(params, c) fused into the step -- the gradients are scaled by
+    min(1, c / (||g|| + 1e-6)), ||g|| over every parameter with a gradient, before the weight decay is added.  The scaling happens
+    on the fly: .grad keeps the unclipped values.  grad_norm: the last step's ||g|| as a 0-d device tensor (no sync).  One param
+    group only (the norm is global).  An optimizer attribute, not a param_groups key, so state_dicts stay the reference's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, skip_nonfinite=False, max_grad_norm=None):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: {}".format(lr))
         if not 0.0 <= eps:
@@ -26,10 +44,18 @@ class diffGradNorm(Optimizer):
             raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
         if not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        max_grad_norm = check_max_grad_norm(max_grad_norm, "camradepth_amd.diffGradNorm")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._groups = None
         self.skip_nonfinite = bool(skip_nonfinite)
         self.found_inf, self.skipped_steps = False, 0
+        self.max_grad_norm, self.grad_norm = max_grad_norm, None
+        self._check_groups()
+
+    def _check_groups(self):
+        if self.max_grad_norm is not None and len(self.param_groups) > 1:
+            raise L.CrdError(f"camradepth_amd.diffGradNorm(max_grad_norm=...) takes one param group, got {len(self.param_groups)}: the "
+                             "clipping norm is global (clip per group with torch.nn.utils.clip_grad_norm_ in an eager loop)")
 
     # ------------------------------------------------------------------ flat layout
     def _build(self, group):
@@ -77,6 +103,7 @@ class diffGradNorm(Optimizer):
         st["active"] = torch.ones(nt, dtype=torch.uint8, device=dev)
         st["step"] = 0
         st["gate"] = None                        # skip_nonfinite: the verdict words (created on the first gated step)
+        st["parts"] = st["clip"] = None          # max_grad_norm: 4 rows of norm parts, [total, coef] (created on the first clipped step)
         for t, (p, o) in enumerate(zip(ps, offs)):
             s = self.state[p]
             s["step"] = 0
@@ -92,6 +119,7 @@ class diffGradNorm(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_groups()
         if self._groups is None:
             self._groups = [self._build(g) for g in self.param_groups]
         lb = L.load()
@@ -130,7 +158,7 @@ class diffGradNorm(Optimizer):
                 st["act_host"] = None
             beta1, beta2 = group["betas"]
             pbase = st["flat_p"].data_ptr() if st["flat_p"] is not None else st["base"]
-            if self.skip_nonfinite:
+            if self.skip_nonfinite or self.max_grad_norm is not None:
                 if not self._gated_step(lb, group, st, ps, pbase, gptr, act_host):
                     self._mark_changed(ps)
                 continue
@@ -154,30 +182,50 @@ class diffGradNorm(Optimizer):
                 ow().mark_params_changed()
 
     def _gated_step(self, lb, group, st, ps, pbase, gptr, act_host):
-        """The gated launches of one group; -> True if the step was skipped."""
-        gate = self._gate(st, ps)
+        """The gated and / or clipped launches of one group (norm pass, then the commit); -> True if the step was skipped."""
+        gate = self._gate(st, ps) if self.skip_nonfinite else None
         active = None if all(act_host) else st["active"].data_ptr()
         beta1, beta2 = group["betas"]
-        L.check(lb.crd_diffgradnorm_norm_gated(pbase, gptr, st["nsq"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(),
-                                               st["b2c"].data_ptr(), st["nblk"], active, float(group["weight_decay"]), None,
-                                               gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
-        L.check(lb.crd_diffgradnorm_commit_gated(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
-                                                 st["egn"].data_ptr(), st["nsq"].data_ptr(), st["fac"].data_ptr(), st["seg"].data_ptr(),
-                                                 st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"], active,
-                                                 float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                                 float(group["weight_decay"]), st["step"] + 1, None, gate.data_ptr(), L.stream()),
-                "crd_diffgradnorm_commit_gated")
+        hyper = (float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]), st["step"] + 1, None)
+        if self.max_grad_norm is None:
+            L.check(lb.crd_diffgradnorm_norm_gated(pbase, gptr, st["nsq"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(),
+                                                   st["b2c"].data_ptr(), st["nblk"], active, float(group["weight_decay"]), None,
+                                                   gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
+            L.check(lb.crd_diffgradnorm_commit_gated(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
+                                                     st["egn"].data_ptr(), st["nsq"].data_ptr(), st["fac"].data_ptr(), st["seg"].data_ptr(),
+                                                     st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"], active, *hyper,
+                                                     gate.data_ptr(), L.stream()), "crd_diffgradnorm_commit_gated")
+        else:
+            if st["parts"] is None:
+                st["parts"] = torch.zeros(4 * st["nblk"], dtype=torch.float32, device=ps[0].device)
+                st["clip"] = torch.zeros(2, dtype=torch.float32, device=ps[0].device)
+            gp = None if gate is None else gate.data_ptr()
+            L.check(lb.crd_diffgradnorm_norm_clip(pbase, gptr, st["parts"].data_ptr(), st["nblk"], st["seg"].data_ptr(),
+                                                  st["b2s"].data_ptr(), st["b2c"].data_ptr(), st["nblk"], active,
+                                                  float(group["weight_decay"]), None, gp, L.stream()), "crd_diffgradnorm_norm_clip")
+            L.check(lb.crd_diffgradnorm_commit_clip(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
+                                                    st["egn"].data_ptr(), st["parts"].data_ptr(), st["nblk"], st["fac"].data_ptr(),
+                                                    st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"],
+                                                    active, *hyper[:6], None, self.max_grad_norm, st["clip"].data_ptr(), gp,
+                                                    L.stream()), "crd_diffgradnorm_commit_clip")
+            self.grad_norm = st["clip"][0].clone()        # (enqueued: no sync)
+        if gate is None:
+            self._count_step(st, ps, act_host)
+            return False
         skipped = bool(int(gate[4]))            # the one read of the step
         gate[:2].zero_()                         # the next window starts without a verdict
         self.found_inf = skipped
         if skipped:
             self.skipped_steps += 1
             return True
+        self._count_step(st, ps, act_host)
+        return False
+
+    def _count_step(self, st, ps, act_host):
         st["step"] += 1
         for p, a_ in zip(ps, act_host):
             if a_:
                 self.state[p]["step"] += 1
-        return False
 
     def _gate(self, st, ps):
         """The group's verdict words; the owning model's backward captures its dropped partials into gate[1] (model._nf_gate)."""

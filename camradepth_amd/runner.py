@@ -14,6 +14,7 @@ from . import lib as L
 from . import losses as HL
 from .inference import InferenceGraph
 from .metrics import DepthMetrics, SegIoU
+from .optim import check_max_grad_norm
 from .trainer import TrainStep, depth_criterion_mode, one_cycle
 
 
@@ -42,7 +43,7 @@ def unpack_batch(batch, input_channels):
 class Trainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, test_dataloader=None, learning_rate=6e-5, num_epochs=1,
                  update_interval=1, div_factor=2.0, max_depth=100.0, max_distances=(100.0, 50.0), num_classes=21, group=None,
-                 use_graph=True, skip_nonfinite=False, criterion=None):
+                 use_graph=True, skip_nonfinite=False, criterion=None, max_grad_norm=None):
         if model.flat is None or not model.flat.is_cuda:
             raise L.CrdError("camradepth_amd.runner.Trainer needs the model on an MI355X (no CPU fallback)")
         self.model, self.cfg = model, model.cfg
@@ -51,6 +52,8 @@ class Trainer:
         self.max_depth, self.max_distances, self.num_classes = max_depth, tuple(max_distances), num_classes
         self.group, self.use_graph = group, use_graph
         self.skip_nonfinite = skip_nonfinite          # GradScaler.step's guard (runner.py:264): TrainStep(skip_nonfinite=...)
+        # clip_grad_norm_ before each optimizer step: TrainStep(max_grad_norm=...), refused here already when it is not > 0
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm, "camradepth_amd.runner.Trainer")
         # runner.py:149; criterion = another {"depth": ..., "seg": ...} of camradepth_amd.losses (TrainStep refuses what it cannot record)
         self.criterion = criterion if criterion is not None else {"depth": HL.MaskedSmoothL1Loss(), "seg": HL.MaskedFocalLoss()}
         depth_criterion_mode(self.criterion)
@@ -73,7 +76,8 @@ class Trainer:
             self._steps[key] = TrainStep(self.model, B, H, W, lr=self.learning_rate, update_interval=self.update_interval,
                                          schedule=one_cycle(max(steps, 2), self.learning_rate, div_factor=self.div_factor),
                                          use_graph=self.use_graph, group=self.group, state=self._train_state,
-                                         skip_nonfinite=self.skip_nonfinite, criterion=self.criterion)
+                                         skip_nonfinite=self.skip_nonfinite, criterion=self.criterion,
+                                         max_grad_norm=self.max_grad_norm)
             self._train_state = self._steps[key].state
         self.step = self._steps[key]
         return self.step

@@ -20,7 +20,7 @@ import torch.distributed as dist
 
 from . import lib as L
 from . import trace
-from .optim import _CHUNK
+from .optim import _CHUNK, check_max_grad_norm
 
 LOSS_W = (1.0, 1.0, 1.0, 0.2, 0.2)   # runner.py:213
 
@@ -121,7 +121,7 @@ class TrainState:
     (plan, static input buffers, captured graphs); the reference's DataLoader has no drop_last (src/data/dataloader.py:40), so
     the last batch of an epoch is smaller and a second TrainStep for that shape must continue THIS state, not restart it."""
 
-    def __init__(self, model, lr, betas, eps, weight_decay, update_interval, schedule):
+    def __init__(self, model, lr, betas, eps, weight_decay, update_interval, schedule, max_grad_norm=None):
         dev = model.flat.device
         n = model.flat.numel()
         self.m, self.v, self.pg = (torch.zeros(n, device=dev) for _ in range(3))
@@ -145,6 +145,11 @@ class TrainState:
         self.hp = torch.zeros(16, device=dev)
         self.hp_ring = [torch.zeros(16).pin_memory() for _ in range(64)]
         self.gate = None             # skip_nonfinite: int32[8] verdict words and step counters on the device (TrainStep._gate)
+        # max_grad_norm: the norm pass's 4 rows of per-workgroup parts and [total, coef] of the last closed window
+        # (include/camradepth_hip.h, crd_diffgradnorm_norm_clip / crd_diffgradnorm_commit_clip)
+        self.max_grad_norm = max_grad_norm
+        self.parts = torch.zeros(4 * self.nblk, device=dev) if max_grad_norm is not None else None
+        self.clip = torch.zeros(2, device=dev) if max_grad_norm is not None else None
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.update_interval = update_interval
         self.schedule = schedule
@@ -156,7 +161,8 @@ class TrainState:
 
 
 _STATE_FIELDS = ("m", "v", "pg", "egn", "fac", "seg", "b2s", "b2c", "nt", "nblk", "nsq", "hp", "hp_ring", "lr", "betas", "eps", "wd",
-                 "update_interval", "schedule", "iter_count", "epoch_iter", "sched_steps", "step_count", "_window_open", "_window_pos", "gate")
+                 "update_interval", "schedule", "iter_count", "epoch_iter", "sched_steps", "step_count", "_window_open", "_window_pos", "gate",
+                 "max_grad_norm", "parts", "clip")
 
 
 class TrainStep:
@@ -175,12 +181,19 @@ class TrainStep:
     skip_nonfinite=True: GradScaler.step's guard (runner.py:264).  An accumulation window whose gradients hold a NaN / inf element,
     or whose backward dropped a non-finite partial from a fixed-point sum, commits nothing: parameters and optimizer state stay
     as they were, the schedule advances, training goes on.  The decision is taken on the device, after the whole backward, so
-    the optimizer of every bucket runs behind the last one (nothing is committed early); found_inf / skipped_steps read it."""
+    the optimizer of every bucket runs behind the last one (nothing is committed early); found_inf / skipped_steps read it.
+
+    max_grad_norm=c: torch.nn.utils.clip_grad_norm_(params, c) between the backward and diffGradNorm, once per accumulation window
+    (after the SUM all-reduce): every gradient is scaled by min(1, c / (||g|| + 1e-6)), ||g|| over the trainable tensors, before
+    the weight decay is added.  The scaling happens on the fly (the flat gradient buffer keeps the unclipped values).  The global
+    norm needs every bucket, so -- as with skip_nonfinite, and sharing its tail when both are on -- the buckets' late-stream
+    slices only write norm parts and the commit of all of them follows the last one.  grad_norm: the window's ||g||, on the
+    device; float('inf') computes it without clipping (the bits of the default step)."""
 
     def __init__(self, model, B, H, W, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, update_interval=1,
-                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False, criterion=None):
+                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False, criterion=None, max_grad_norm=None):
         """state: the TrainState of another TrainStep of the same model (another batch shape of the same run) to continue;
-        lr / betas / eps / weight_decay / update_interval / schedule are then taken from it."""
+        lr / betas / eps / weight_decay / update_interval / schedule / max_grad_norm are then taken from it."""
         assert model.training, "TrainStep drives the training path: call model.train() first"
         self._depth_mode, self._berhu_thresh = depth_criterion_mode(criterion)      # refused here, before anything is allocated
         assert update_interval >= 1
@@ -189,9 +202,11 @@ class TrainStep:
             raise L.CrdError("TrainStep(skip_nonfinite=True) does not support fp8 data gradients (model.fp8_grad): a skipped step "
                              "would poison the delayed scales")
         self.skip_nonfinite = bool(skip_nonfinite)
+        max_grad_norm = check_max_grad_norm(max_grad_norm, "TrainStep")
         if state is not None and state.m.numel() != model.flat.numel():
             raise L.CrdError("TrainStep(state=...): the state belongs to a model with a different parameter count")
-        self.state = state if state is not None else TrainState(model, lr, betas, eps, weight_decay, update_interval, schedule)
+        self.state = state if state is not None else TrainState(model, lr, betas, eps, weight_decay, update_interval, schedule,
+                                                                max_grad_norm)
         self.model, self.B, self.H, self.W = model, B, H, W
         self.dev = model.flat.device
         self.lib = L.load()
@@ -255,6 +270,12 @@ class TrainStep:
     def committed_steps(self):
         """Optimizer steps that changed the parameters: the bias-correction count, and the per-parameter `step` of a checkpoint."""
         return self.step_count if self.gate is None else int(self.gate[2])
+
+    @property
+    def grad_norm(self):
+        """max_grad_norm: ||g|| of the last closed accumulation window before clipping (clip_grad_norm_'s return value), a 0-d fp32
+        device tensor taken in stream order (no sync); None without max_grad_norm."""
+        return None if self.clip is None else self.clip[0].clone()
 
     def optimizer_state(self):
         """diffGradNorm's state in the reference's per-parameter form (diffGradNorm.py:63-71), with `step` = committed steps: what
@@ -372,11 +393,44 @@ class TrainStep:
                 "crd_diffgradnorm_commit_gated")
         self.plan.pack()
 
+    # max_grad_norm pieces: the norm pass that also writes the parts of the global norm (per bucket or all; gated with
+    # skip_nonfinite), and the commit: total + coefficient, every tensor's scalar and update, the re-pack
+    def _norm_clip(self, key=None):
+        m = self.model
+        b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
+        L.check(self.lib.crd_diffgradnorm_norm_clip(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.parts.data_ptr() + 4 * b0, self.nblk,
+                                                    self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0, self.b2c.data_ptr() + 4 * b0, nb,
+                                                    None if mask is None else mask.data_ptr(), 0.0, self.hp.data_ptr(),
+                                                    self.gate.data_ptr() if self.skip_nonfinite else None, L.stream()),
+                "crd_diffgradnorm_norm_clip")
+
+    def _commit_clip(self):
+        m, mask = self.model, self.trainable_mask
+        L.check(self.lib.crd_diffgradnorm_commit_clip(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                      self.pg.data_ptr(), self.egn.data_ptr(), self.parts.data_ptr(), self.nblk,
+                                                      self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(),
+                                                      self.nt, self.nblk, None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0,
+                                                      0.0, 1, self.hp.data_ptr(), self.max_grad_norm, self.clip.data_ptr(),
+                                                      self.gate.data_ptr() if self.skip_nonfinite else None, L.stream()),
+                "crd_diffgradnorm_commit_clip")
+        self.plan.pack()
+
+    def _deferred(self):
+        """(norm pass, commit) when the optimizer step waits for a global decision -- skip_nonfinite's verdict, max_grad_norm's
+        norm -- or None: the default step, whose buckets update as soon as their gradients are final."""
+        if getattr(self, "max_grad_norm", None) is not None:
+            return self._norm_clip, self._commit_clip
+        if getattr(self, "skip_nonfinite", False):
+            return self._norm_gated, self._commit_gated
+        return None
+
     def _segments(self):
         """The iteration as a list of (callable, bucket-to-launch-after | None | 'loss' | 'gate'), for the current
         (self._zero, self._opt): zero the gradients first / all-reduce and run the optimizer last.  skip_nonfinite: the backward is
-        bracketed by flag captures, then the gated norm ('gate': the ranks combine their verdicts here) and the gated commit."""
+        bracketed by flag captures, then the gated norm ('gate': the ranks combine their verdicts here) and the gated commit.
+        max_grad_norm: the norm pass and the commit follow the whole backward (and its all-reduce) the same way."""
         skip = getattr(self, "skip_nonfinite", False)
+        deferred = self._deferred()
         segs = [(self._forward_and_loss_partials, "loss")]
         first = True
         for key in GradSync.ORDER:
@@ -390,14 +444,18 @@ class TrainStep:
                     self.grad_hook(key)
             segs.append((run, key if self._opt else None))
             first = False
-        if skip:
-            def tail(opt=self._opt):
-                self._capture_flags(True)
-                if opt:
-                    self._norm_gated()
-            segs.append((tail, "gate" if self._opt and self.dist_active else None))
+        if deferred is not None:
+            norm, commit = deferred
+            if skip:
+                def tail(opt=self._opt):
+                    self._capture_flags(True)
+                    if opt:
+                        norm()
+                segs.append((tail, "gate" if self._opt and self.dist_active else None))
+            elif self._opt:
+                segs.append((norm, None))
             if self._opt:
-                segs.append((self._commit_gated, None))
+                segs.append((commit, None))
         elif self._opt:
             segs.append((self._optimizer, None))
         return segs
@@ -414,7 +472,7 @@ class TrainStep:
         changes is restored afterwards."""
         self.plan.ensure_packed()
         keep = (self.model.flat, self.m, self.v, self.pg, self.egn, self.nsq, self.fac, self.model.flat_grad) + \
-            ((self.gate,) if self.skip_nonfinite else ())
+            ((self.gate,) if self.skip_nonfinite else ()) + ((self.parts, self.clip) if self.max_grad_norm is not None else ())
         saved = [t.clone() for t in keep]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -451,8 +509,10 @@ class TrainStep:
             # Multi-GPU: the loss all-reduce follows the first graph, and each bucket's gradient all-reduce is enqueued
             # behind its late graph (last iteration of an accumulation window only).
             # skip_nonfinite: the late graphs and the per-bucket slices only run the gated norm (finiteness test included); the
-            # flag capture, the commit of every bucket and the re-pack follow the LAST bucket, on the main stream (tail graphs)
+            # flag capture, the commit of every bucket and the re-pack follow the LAST bucket, on the main stream (tail graphs);
+            # max_grad_norm: the same order (the slices write the parts of the global norm), one shared tail with skip_nonfinite
             skip = self.skip_nonfinite
+            deferred = self._deferred()
             segs = self._segments()
             main = torch.cuda.current_stream()
             bsegs = segs[1:1 + len(GradSync.ORDER)]
@@ -479,7 +539,7 @@ class TrainStep:
                     if skip and getattr(self, "grad_hook", None) is not None:
                         self.grad_hook(key)         # tests: runs (captured) where this bucket's gradients have become final
                     if opt and not self.dist_active:    # this bucket's gradients are final: its optimizer slice follows at once
-                        self._norm_gated(key) if skip else self._optimizer(key)
+                        deferred[0](key) if deferred else self._optimizer(key)
                 gopt = None
                 if opt and self.dist_active:
                     # multi-GPU: the bucket's optimizer slice is a graph of its own, replayed on the late stream behind THAT
@@ -487,22 +547,26 @@ class TrainStep:
                     # backward and only the last bucket's slice is exposed
                     gopt = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gopt, stream=self.late_stream):
-                        self._norm_gated(key) if skip else self._optimizer(key)
+                        deferred[0](key) if deferred else self._optimizer(key)
                 main.wait_stream(self.late_stream)
                 chain.append((g, gl, key, gopt))
             tail = None
-            if skip:                                         # (the flag capture + commit, and -- multi-GPU -- the commit after the ranks agree)
-                gt = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gt):
-                    self._capture_flags(True)
-                    if opt and not self.dist_active:
-                        self._commit_gated()
-                gc = None
-                if opt and self.dist_active:
+            if deferred:                                     # (the flag capture + commit, and -- multi-GPU -- the commit after the ranks agree)
+                agree = skip and self.dist_active
+                gt = gc = None
+                if skip or (opt and not agree):
+                    gt = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gt):
+                        if skip:
+                            self._capture_flags(True)
+                        if opt and not agree:
+                            deferred[1]()
+                if opt and agree:
                     gc = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gc):
-                        self._commit_gated()
-                tail = (gt, gc)
+                        deferred[1]()
+                if gt is not None or gc is not None:
+                    tail = (gt, gc)
             return [(("late", g0, chain, tail), None)]
         if not self.dist_active:      # no collective between the segments: the whole step is one graph (five fewer launches)
             g = torch.cuda.CUDAGraph()
@@ -559,7 +623,8 @@ class TrainStep:
             e1.record(main)
             probe.append((e0, e1))
         if isinstance(go, tuple):              # skip_nonfinite: flag capture (+ commit); multi-GPU: the ranks agree, then the commit
-            go[0].replay()
+            if go[0] is not None:              # (max_grad_norm alone: the commit)
+                go[0].replay()
             if go[1] is not None:
                 self._agree()
                 go[1].replay()

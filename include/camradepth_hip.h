@@ -64,7 +64,7 @@ int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
 int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 7        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 8        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -694,6 +694,26 @@ int crd_diffgradnorm_commit_gated(float* p, const float* g, float* exp_avg, floa
                                   const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
                                   const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
                                   int32_t step, const float* hp_dev, int32_t* gate, crd_stream_t stream);
+/* The optimizer step behind torch.nn.utils.clip_grad_norm_(params, max_norm) (max_grad_norm): every gradient is scaled by
+ * coef = min(1, max_norm / (total + 1e-6)), total = the 2-norm over all blocks given, before the weight decay is added; the norm,
+ * exp_avg, exp_avg_sq and previous_grad all see the scaled gradient.  The gradient buffer itself is not written.
+ * parts: device float[4 * parts_stride], four rows of per-workgroup parts: [0] sum (g + wd p)^2 (what norm_sq holds above), [1] sum
+ * g^2, [2] sum g p and [3] sum p^2 (rows 2 and 3: with weight decay only).  norm_clip: k_dgn_norm's pass over the blocks given, which
+ * also writes rows 1-3 (one bucket may be passed at a time, as for norm_gated: `parts` then points at that bucket's first block
+ * and parts_stride stays the full count); gate (optional): the finiteness test of norm_gated.  commit_clip: ONE workgroup adds row 1
+ * over all n_blocks in a fixed order in fp64 and writes clip[0] = total, clip[1] = coef (device float[2]; torch's fp32 coefficient,
+ * a NaN total gives NaN), then the per-tensor scalars (from row 0 when coef == 1, else from rows 1-3) and the update.  coef == 1
+ * gives the bits of crd_diffgradnorm_step / crd_diffgradnorm_commit_gated.  gate (optional): crd_diffgradnorm_commit_gated's
+ * semantics (gate[0] set by norm_clip).  max_norm > 0; +inf gives coef = 1 (the total only). */
+int crd_diffgradnorm_norm_clip(const float* p, const float* g, float* parts, int64_t parts_stride, const int64_t* seg_off,
+                               const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active,
+                               float weight_decay, const float* hp_dev, int32_t* gate, crd_stream_t stream);
+int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                 float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
+                                 const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
+                                 int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
+                                 int32_t* gate, crd_stream_t stream);
 
 #ifdef __cplusplus
 }
