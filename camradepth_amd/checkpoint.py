@@ -60,7 +60,9 @@ def load_trainstep_optimizer_state(ts, osd):
 
 def save_checkpoint(path, model, optimizer=None, steps=(0, 0)):
     """Same dictionary as runner.py:369 (tensors moved to the CPU; the model itself stays on its device).  optimizer: a torch
-    optimizer (camradepth_amd.diffGradNorm) or a TrainStep (trainstep_optimizer_state_dict)."""
+    optimizer (camradepth_amd.diffGradNorm) or a TrainStep (trainstep_optimizer_state_dict).  A TrainStep that keeps an EMA of the
+    weights (ema_decay) adds "ema_state_dict" (the averaged weights under the model's keys), "ema_decay" and "ema_updates"; without
+    one the key set is the reference's.  Inside ts.ema_weights() the two sets are exchanged, and so are the two entries."""
     state = {"state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "steps": list(steps)}
     if optimizer is not None:
         osd = trainstep_optimizer_state_dict(optimizer) if hasattr(optimizer, "optimizer_state") else optimizer.state_dict()
@@ -70,13 +72,18 @@ def save_checkpoint(path, model, optimizer=None, steps=(0, 0)):
                     st[k] = v.detach().cpu().clone()
         state["optimizer"] = osd
         state["lr"] = osd["param_groups"][0]["lr"] if hasattr(optimizer, "optimizer_state") else optimizer.param_groups[0]["lr"]
+        if hasattr(optimizer, "ema_state_dict") and getattr(optimizer, "ema", None) is not None:
+            state["ema_state_dict"] = {k: v.detach().cpu().clone() for k, v in optimizer.ema_state_dict().items()}
+            state["ema_decay"], state["ema_updates"] = optimizer.ema_decay, optimizer.ema_updates
     torch.save(state, path)
     return state
 
 
 def load_checkpoint(path_or_state, model, optimizer=None, shape_match=True):
     """Loads `state_dict` (with the reference's shape-matching rule unless shape_match=False) and, if given and present,
-    the optimizer state.  Returns (missing, mismatched, steps)."""
+    the optimizer state.  Returns (missing, mismatched, steps).  A TrainStep with ema_decay gets its EMA and update count back from
+    "ema_state_dict" / "ema_updates" (entries whose shape matches, the rest keep the loaded weights); from a checkpoint without them
+    the EMA is re-seeded from the loaded weights with the count at 0.  (model.load_state_dict() alone does not touch the EMA.)"""
     state = torch.load(path_or_state, map_location="cpu", weights_only=False) if isinstance(path_or_state, str) else path_or_state
     sd = state["state_dict"] if "state_dict" in state else state
     if shape_match:
@@ -89,4 +96,12 @@ def load_checkpoint(path_or_state, model, optimizer=None, shape_match=True):
             load_trainstep_optimizer_state(optimizer, state["optimizer"])
         else:
             optimizer.load_state_dict(state["optimizer"])
+    if optimizer is not None and hasattr(optimizer, "ema_state_dict") and getattr(optimizer, "ema", None) is not None:
+        optimizer.reseed_ema(0)
+        if "ema_state_dict" in state:
+            src = strip_module_prefix(state["ema_state_dict"])
+            for k, dst in optimizer.ema_state_dict().items():
+                if k in src and tuple(src[k].shape) == tuple(dst.shape):
+                    dst.copy_(torch.as_tensor(src[k]))
+            optimizer._set_ema_updates(int(state.get("ema_updates", 0)))
     return missing, mismatched, state.get("steps", [0, 0])

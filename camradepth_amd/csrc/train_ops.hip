@@ -342,16 +342,38 @@ __global__ __launch_bounds__(256) void k_dgn_scalar(float* exp_grad_norm, const 
   }
 }
 
+// ema_decay: the weight of step n of the parameters' exponential moving average, w_n = 1 - d_n, d_n = min(decay, (1 + n) / (10 + n))
+// with the warm-up (timm's rule), else decay.  ONE fp32 expression for the host (ungated paths: it knows n) and the device (gated
+// commit: only the device knows how many steps were committed), so that every path forms the same bits.
+__host__ __device__ __forceinline__ float dgn_ema_weight(float decay, int warmup, int n) {
+  const float d = warmup ? fminf(decay, (float)(1 + n) / (float)(10 + n)) : decay;
+  return 1.0f - d;
+}
+// e: the EMA buffer (layout of p).  w: w_n of this step (hp[5] when hp is given).  Gated: decay / warmup / base (hp[6], int32 at hp[15] /
+// hp[7] when hp is given), base = gate[2] when the EMA was created or restored: n = committed steps since then.
+struct DgnEma { float* e; float w; float decay; int warmup; int base; };
+
 // CLIP: g <- c g (c = clip[1]) before the weight decay is added; c == 1 leaves every bit as it is
-template <bool GATED, bool CLIP = false>
+// EMA: e <- fmaf(w_n, p_new - e, e) on the value about to be stored (in a register: one more load and store per element, same
+// lane -> address map as p, so the stream coalesces as p's does); frozen tensors and skipped windows return above it
+template <bool GATED, bool CLIP = false, bool EMA = false>
 __global__ __launch_bounds__(TPB) void k_dgn_update(float* p, const float* g, float* m, float* v, float* pg, const float* factor,
                                                     const long long* seg_off, const int* blk2seg, const int* blk2chunk,
                                                     const unsigned char* active, float beta1, float beta2, float eps, float wd,
-                                                    float step_size, const float* hp, const int* gate, const float* clip = nullptr) {
+                                                    float step_size, const float* hp, const int* gate, const float* clip = nullptr,
+                                                    DgnEma ea = DgnEma{}) {
   if (hp) { beta1 = hp[0]; beta2 = hp[1]; eps = hp[2]; wd = hp[3]; step_size = hp[4]; }
   if (GATED) {
     if (gate[4]) return;                                   // the window saw a non-finite gradient: nothing is written
     step_size = __int_as_float(gate[5]);
+  }
+  float ew = 0.f;
+  if (EMA) {
+    ew = hp ? hp[5] : ea.w;
+    if (GATED) {                                           // (gate[2]: this step included, k_dgn_scalar counted it)
+      const int* hi = reinterpret_cast<const int*>(hp);
+      ew = hp ? dgn_ema_weight(hp[6], hi[15], gate[2] - hi[7]) : dgn_ema_weight(ea.decay, ea.warmup, gate[2] - ea.base);
+    }
   }
   const int t = blk2seg[blockIdx.x];
   if (active && !active[t]) return;
@@ -374,7 +396,30 @@ __global__ __launch_bounds__(TPB) void k_dgn_update(float* p, const float* g, fl
     const float vv = beta2 * v[i] + (1.f - beta2) * gv * gv;
     const float dfc = 1.f / (1.f + expf(-fabsf(pg[i] - gv)));
     m[i] = mv; v[i] = vv; pg[i] = gv;
-    p[i] = pv - step_size * (mv * dfc) / (sqrtf(vv) + eps);
+    const float pn = pv - step_size * (mv * dfc) / (sqrtf(vv) + eps);
+    p[i] = pn;
+    if (EMA) {
+      const float ev = ea.e[i];
+      ea.e[i] = fmaf(ew, pn - ev, ev);
+    }
+  }
+}
+
+// crd_swap_f32: a[i] <-> b[i].  `head` leading and the trailing elements one by one, nvec float4 pairs between them (16-byte loads
+// and stores: the host picked head so that both are aligned there, or nvec = 0).  Every element belongs to exactly one lane.
+__global__ __launch_bounds__(TPB) void k_swap_f32(float* a, float* b, long long n, long long head, long long nvec) {
+  const long long tid = (long long)blockIdx.x * TPB + threadIdx.x, stride = (long long)gridDim.x * TPB;
+  float4* a4 = reinterpret_cast<float4*>(a + head);
+  float4* b4 = reinterpret_cast<float4*>(b + head);
+  for (long long i = tid; i < nvec; i += stride) {
+    const float4 x = a4[i], y = b4[i];
+    a4[i] = y; b4[i] = x;
+  }
+  const long long tail0 = head + 4 * nvec, rem = head + (n - tail0);
+  for (long long i = tid; i < rem; i += stride) {
+    const long long j = i < head ? i : tail0 + (i - head);
+    const float x = a[j], y = b[j];
+    a[j] = y; b[j] = x;
   }
 }
 
@@ -569,14 +614,11 @@ extern "C" int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int3
   return CRD_OK;
 }
 
-extern "C" int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                     float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
-                                     const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                     const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                     int32_t step, const float* hp_dev, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
-                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1,
-                "crd_diffgradnorm_step: bad argument");
+// One body per commit path; `ema` = nullptr launches today's instantiation of the update (the entry points without _ema)
+static int dgn_step(const char* who, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad, float* exp_grad_norm,
+                    float* norm_sq, float* factor, const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk,
+                    int32_t n_tensors, int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, int32_t step, const float* hp_dev, const DgnEma* ema, crd_stream_t stream) {
   hipStream_t st = as_stream(stream);
   const long long* so = reinterpret_cast<const long long*>(seg_off);
   hipLaunchKernelGGL(k_dgn_norm<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, so, blk2seg, blk2chunk, weight_decay, hp_dev, norm_sq, active,
@@ -585,10 +627,42 @@ extern "C" int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, f
                      blk2seg, n_blocks, nullptr, nullptr, DgnGateHost{0.f, 0});
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
-  hipLaunchKernelGGL(k_dgn_update<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
-                     blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr);
-  CRD_LAUNCH_CHECK("crd_diffgradnorm_step");
+  if (ema)
+    hipLaunchKernelGGL((k_dgn_update<false, false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, nullptr, *ema);
+  else
+    hipLaunchKernelGGL(k_dgn_update<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
+                       blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr);
+  CRD_LAUNCH_CHECK(who);
   return CRD_OK;
+}
+
+#define DGN_EMA_ARGS_OK(e, d, n) ((e) && (d) >= 0.f && (d) < 1.f && (n) >= 0)
+
+extern "C" int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                     float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
+                                     const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                                     const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                     int32_t step, const float* hp_dev, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
+                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1,
+                "crd_diffgradnorm_step: bad argument");
+  return dgn_step("crd_diffgradnorm_step", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off, blk2seg, blk2chunk,
+                  n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, nullptr, stream);
+}
+
+extern "C" int crd_diffgradnorm_step_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                         float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
+                                         const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                                         const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                         int32_t step, const float* hp_dev, float* ema, float ema_decay, int32_t ema_warmup,
+                                         int32_t ema_n, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
+                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && DGN_EMA_ARGS_OK(ema, ema_decay, ema_n) && (hp_dev || ema_n >= 1),
+                "crd_diffgradnorm_step_ema: bad argument");
+  const DgnEma ea{ema, dgn_ema_weight(ema_decay, ema_warmup, ema_n), ema_decay, ema_warmup, 0};
+  return dgn_step("crd_diffgradnorm_step_ema", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off, blk2seg,
+                  blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, &ea, stream);
 }
 
 // ---- gated diffGradNorm (skip_nonfinite): include/camradepth_hip.h ----
@@ -602,6 +676,27 @@ extern "C" int crd_diffgradnorm_norm_gated(const float* p, const float* g, float
   return CRD_OK;
 }
 
+static int dgn_commit_gated(const char* who, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                            float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off, const int32_t* blk2seg,
+                            const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks, const uint8_t* active, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, int32_t step, const float* hp_dev, int32_t* gate,
+                            const DgnEma* ema, crd_stream_t stream) {
+  hipStream_t st = as_stream(stream);
+  const long long* so = reinterpret_cast<const long long*>(seg_off);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
+  hipLaunchKernelGGL(k_dgn_scalar<true>, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so,
+                     blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step});
+  if (ema)
+    hipLaunchKernelGGL((k_dgn_update<true, false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, nullptr, *ema);
+  else
+    hipLaunchKernelGGL(k_dgn_update<true>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
+                       blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, gate);
+  CRD_LAUNCH_CHECK(who);
+  return CRD_OK;
+}
+
 extern "C" int crd_diffgradnorm_commit_gated(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
                                              float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
                                              const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
@@ -610,16 +705,24 @@ extern "C" int crd_diffgradnorm_commit_gated(float* p, const float* g, float* ex
   CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
                     blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && gate,
                 "crd_diffgradnorm_commit_gated: bad argument");
-  hipStream_t st = as_stream(stream);
-  const long long* so = reinterpret_cast<const long long*>(seg_off);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
-  hipLaunchKernelGGL(k_dgn_scalar<true>, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so,
-                     blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step});
-  hipLaunchKernelGGL(k_dgn_update<true>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
-                     blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, gate);
-  CRD_LAUNCH_CHECK("crd_diffgradnorm_commit_gated");
-  return CRD_OK;
+  return dgn_commit_gated("crd_diffgradnorm_commit_gated", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off,
+                          blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, gate, nullptr,
+                          stream);
+}
+
+extern "C" int crd_diffgradnorm_commit_gated_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                                 float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
+                                                 const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                                                 const uint8_t* active, float lr, float beta1, float beta2, float eps,
+                                                 float weight_decay, int32_t step, const float* hp_dev, int32_t* gate, float* ema,
+                                                 float ema_decay, int32_t ema_warmup, int32_t ema_base, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
+                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && gate && DGN_EMA_ARGS_OK(ema, ema_decay, ema_base),
+                "crd_diffgradnorm_commit_gated_ema: bad argument");
+  const DgnEma ea{ema, 0.f, ema_decay, ema_warmup, ema_base};
+  return dgn_commit_gated("crd_diffgradnorm_commit_gated_ema", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off,
+                          blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, gate, &ea,
+                          stream);
 }
 
 // ---- diffGradNorm with global gradient-norm clipping (max_grad_norm): include/camradepth_hip.h ----
@@ -639,15 +742,11 @@ extern "C" int crd_diffgradnorm_norm_clip(const float* p, const float* g, float*
   return CRD_OK;
 }
 
-extern "C" int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                            float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
-                                            const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
-                                            int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
-                                            float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
-                                            int32_t* gate, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && parts && parts_stride >= n_blocks && factor && seg_off &&
-                    blk2seg && blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && max_norm > 0.f && clip,
-                "crd_diffgradnorm_commit_clip: bad argument");
+static int dgn_commit_clip(const char* who, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                           float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor, const int64_t* seg_off,
+                           const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks, const uint8_t* active,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* hp_dev,
+                           float max_norm, float* clip, int32_t* gate, const DgnEma* ema, crd_stream_t stream) {
   hipStream_t st = as_stream(stream);
   const long long* so = reinterpret_cast<const long long*>(seg_off);
   const long long ps = parts_stride;
@@ -657,15 +756,71 @@ extern "C" int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp
   if (gate) {
     hipLaunchKernelGGL((k_dgn_scalar<true, true>), dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, parts, factor, active, n_tensors,
                        so, blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step}, weight_decay, (const float*)clip, ps);
-    hipLaunchKernelGGL((k_dgn_update<true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, (const float*)clip);
+    if (ema)
+      hipLaunchKernelGGL((k_dgn_update<true, true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, (const float*)clip,
+                         *ema);
+    else
+      hipLaunchKernelGGL((k_dgn_update<true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, (const float*)clip);
   } else {
     hipLaunchKernelGGL((k_dgn_scalar<false, true>), dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, parts, factor, active,
                        n_tensors, so, blk2seg, n_blocks, nullptr, hp_dev, DgnGateHost{0.f, 0}, weight_decay, (const float*)clip, ps);
-    hipLaunchKernelGGL((k_dgn_update<false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, (const float*)clip);
+    if (ema)
+      hipLaunchKernelGGL((k_dgn_update<false, true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, (const float*)clip, *ema);
+    else
+      hipLaunchKernelGGL((k_dgn_update<false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
+                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, (const float*)clip);
   }
-  CRD_LAUNCH_CHECK("crd_diffgradnorm_commit_clip");
+  CRD_LAUNCH_CHECK(who);
+  return CRD_OK;
+}
+
+extern "C" int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                            float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
+                                            const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
+                                            int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
+                                            float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
+                                            int32_t* gate, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && parts && parts_stride >= n_blocks && factor && seg_off &&
+                    blk2seg && blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && max_norm > 0.f && clip,
+                "crd_diffgradnorm_commit_clip: bad argument");
+  return dgn_commit_clip("crd_diffgradnorm_commit_clip", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, parts, parts_stride, factor,
+                         seg_off, blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev,
+                         max_norm, clip, gate, nullptr, stream);
+}
+
+extern "C" int crd_diffgradnorm_commit_clip_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                                float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
+                                                const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk,
+                                                int32_t n_tensors, int32_t n_blocks, const uint8_t* active, float lr, float beta1,
+                                                float beta2, float eps, float weight_decay, int32_t step, const float* hp_dev,
+                                                float max_norm, float* clip, int32_t* gate, float* ema, float ema_decay,
+                                                int32_t ema_warmup, int32_t ema_n, crd_stream_t stream) {
+  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && parts && parts_stride >= n_blocks && factor && seg_off &&
+                    blk2seg && blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && max_norm > 0.f && clip &&
+                    DGN_EMA_ARGS_OK(ema, ema_decay, ema_n) && (gate || hp_dev || ema_n >= 1),
+                "crd_diffgradnorm_commit_clip_ema: bad argument");
+  // ema_n: without a gate the number n of this EMA update, with one the base of crd_diffgradnorm_commit_gated_ema
+  const DgnEma ea{ema, gate ? 0.f : dgn_ema_weight(ema_decay, ema_warmup, ema_n), ema_decay, ema_warmup, gate ? ema_n : 0};
+  return dgn_commit_clip("crd_diffgradnorm_commit_clip_ema", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, parts, parts_stride,
+                         factor, seg_off, blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step,
+                         hp_dev, max_norm, clip, gate, &ea, stream);
+}
+
+extern "C" int crd_swap_f32(float* a, float* b, int64_t n, crd_stream_t stream) {
+  CRD_CHECK_ARG(n >= 0 && (n == 0 || (a && b)) && ((uintptr_t)a & 3) == 0 && ((uintptr_t)b & 3) == 0 &&
+                    (n == 0 || a + n <= b || b + n <= a),
+                "crd_swap_f32: bad argument (two non-overlapping fp32 buffers)");
+  if (n == 0) return CRD_OK;
+  long long head = (long long)(((16 - ((uintptr_t)a & 15)) & 15) / 4), nvec = 0;      // elements up to a's first 16-byte boundary
+  if (head > n) head = n;
+  if ((((uintptr_t)(b + head)) & 15) == 0) nvec = (n - head) / 4;
+  else head = 0;                                                                      // a and b misaligned differently: one by one
+  const long long work = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
+  hipLaunchKernelGGL(k_swap_f32, dim3(blocks_for(work, 4096)), dim3(TPB), 0, as_stream(stream), a, b, (long long)n, head, nvec);
+  CRD_LAUNCH_CHECK("crd_swap_f32");
   return CRD_OK;
 }
 

@@ -90,7 +90,7 @@ class UnpackEntry(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 8          # include/camradepth_hip.h: CRD_ABI_VERSION
+ABI_VERSION = 9          # include/camradepth_hip.h: CRD_ABI_VERSION
 
 
 def load():
@@ -151,6 +151,8 @@ _SIGS = {
     "crd_nonfinite_status": "ip", "crd_nonfinite_capture": "pp",
     "crd_diffgradnorm_norm_gated": "ppppppipfppp", "crd_diffgradnorm_commit_gated": "pppppppppppiipfffffippp",
     "crd_diffgradnorm_norm_clip": "ppplpppipfppp", "crd_diffgradnorm_commit_clip": "ppppppplppppiipfffffipfppp",
+    "crd_diffgradnorm_step_ema": "pppppppppppiipfffffippfiip", "crd_diffgradnorm_commit_gated_ema": "pppppppppppiipfffffipppfiip",
+    "crd_diffgradnorm_commit_clip_ema": "ppppppplppppiipfffffipfpppfiip", "crd_swap_f32": "pplp",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "L": C.c_uint64, "f": C.c_float}
 EXPORTS = list(_SIGS)

@@ -4,6 +4,7 @@ Same constructor, `param_groups` and per-parameter `state` keys as the reference
 (src/models/diffGradNorm.py:26-37,63-71) so `OneCycleLR(cycle_momentum=True)` can drive `lr` and
 `betas[0]` every iteration (src/main/runner.py:151-152,270) and optimizer state_dicts interchange.
 """
+import numpy as np
 import torch
 from torch.optim.optimizer import Optimizer
 
@@ -25,6 +26,29 @@ def check_max_grad_norm(value, who):
     return v
 
 
+def check_ema_decay(value, who):
+    """None (no EMA of the weights) or its decay d, 0 <= d < 1 -> float | None, or CrdError."""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not 0.0 <= v < 1.0:          # (NaN fails this too)
+        raise L.CrdError(f"{who}(ema_decay={value!r}): ema_decay must be a number with 0 <= ema_decay < 1")
+    return v
+
+
+def ema_weight(decay, warmup, n):
+    """(d_n, w_n) of EMA update n = 1, 2, ... as Python floats holding fp32 values: d_n = min(decay, (1 + n) / (10 + n)) with the
+    warm-up (timm's rule), else decay; w_n = 1 - d_n.  The fp32 expression of the kernels (csrc/train_ops.hip: dgn_ema_weight), so
+    the w_n the host uploads and the one the gated commit forms on the device are the same bits."""
+    d = np.float32(decay)
+    if warmup:
+        d = min(d, np.float32(1 + n) / np.float32(10 + n))
+    return float(d), float(np.float32(1.0) - d)
+
+
 class diffGradNorm(Optimizer):
     """skip_nonfinite=True: GradScaler.step's guard on the gated kernels -- a step whose gradients hold a NaN / inf element, or whose
     backward dropped a non-finite partial from a fixed-point sum (camradepth_amd.CamRaDepth's backward), writes nothing and does
@@ -33,9 +57,16 @@ class diffGradNorm(Optimizer):
     max_grad_norm=c: torch.nn.utils.clip_grad_norm_(params, c) fused into the step -- the gradients are scaled by
     min(1, c / (||g|| + 1e-6)), ||g|| over every parameter with a gradient, before the weight decay is added.  The scaling happens
     on the fly: .grad keeps the unclipped values.  grad_norm: the last step's ||g|| as a 0-d device tensor (no sync).  One param
-    group only (the norm is global).  An optimizer attribute, not a param_groups key, so state_dicts stay the reference's."""
+    group only (the norm is global).  An optimizer attribute, not a param_groups key, so state_dicts stay the reference's.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, skip_nonfinite=False, max_grad_norm=None):
+    ema_decay=d (0 <= d < 1): an exponential moving average of the parameters kept by the update kernel itself, one fp32 buffer per
+    param group seeded with the parameters when the group is first laid out: every committed step n = 1, 2, ... does
+    e <- e + w_n (p_new - e), w_n = 1 - min(d, (1 + n) / (10 + n)) with ema_warmup (timm's rule), else 1 - d.  Parameters without a
+    gradient and skipped steps leave it untouched.  ema_state() maps each parameter to its EMA view.  Any number of param groups;
+    like max_grad_norm an optimizer attribute, not a param_groups key, and not part of state_dict()."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, skip_nonfinite=False, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=True):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: {}".format(lr))
         if not 0.0 <= eps:
@@ -45,11 +76,13 @@ class diffGradNorm(Optimizer):
         if not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
         max_grad_norm = check_max_grad_norm(max_grad_norm, "camradepth_amd.diffGradNorm")
+        ema_decay = check_ema_decay(ema_decay, "camradepth_amd.diffGradNorm")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._groups = None
         self.skip_nonfinite = bool(skip_nonfinite)
         self.found_inf, self.skipped_steps = False, 0
         self.max_grad_norm, self.grad_norm = max_grad_norm, None
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self._check_groups()
 
     def _check_groups(self):
@@ -104,6 +137,11 @@ class diffGradNorm(Optimizer):
         st["step"] = 0
         st["gate"] = None                        # skip_nonfinite: the verdict words (created on the first gated step)
         st["parts"] = st["clip"] = None          # max_grad_norm: 4 rows of norm parts, [total, coef] (created on the first clipped step)
+        st["ema"], st["ema_n"] = None, 0         # ema_decay: the group's EMA (layout of the parameters' flat span), its update count
+        if self.ema_decay is not None:
+            st["ema"] = torch.zeros(span, dtype=torch.float32, device=dev)
+            for p, o in zip(ps, offs):
+                st["ema"][o:o + p.numel()].copy_(p.detach().reshape(-1))
         for t, (p, o) in enumerate(zip(ps, offs)):
             s = self.state[p]
             s["step"] = 0
@@ -163,12 +201,15 @@ class diffGradNorm(Optimizer):
                     self._mark_changed(ps)
                 continue
             st["step"] += 1
-            L.check(lb.crd_diffgradnorm_step(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
-                                             st["egn"].data_ptr(), st["nsq"].data_ptr(), st["fac"].data_ptr(),
-                                             st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps),
-                                             st["nblk"], None if all(act_host) else st["active"].data_ptr(), float(group["lr"]),
-                                             float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                             st["step"], None, L.stream()), "crd_diffgradnorm_step")
+            args = (pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(), st["egn"].data_ptr(), st["nsq"].data_ptr(),
+                    st["fac"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"],
+                    None if all(act_host) else st["active"].data_ptr(), float(group["lr"]), float(beta1), float(beta2),
+                    float(group["eps"]), float(group["weight_decay"]), st["step"], None)
+            if st["ema"] is not None:
+                st["ema_n"] += 1
+                L.check(lb.crd_diffgradnorm_step_ema(*args, *self._ema_args(st, False), L.stream()), "crd_diffgradnorm_step_ema")
+            else:
+                L.check(lb.crd_diffgradnorm_step(*args, L.stream()), "crd_diffgradnorm_step")
             for p, a_ in zip(ps, act_host):
                 if a_:
                     self.state[p]["step"] += 1
@@ -181,6 +222,19 @@ class diffGradNorm(Optimizer):
             if ow is not None and ow() is not None:
                 ow().mark_params_changed()
 
+    def _ema_args(self, st, gated):
+        """The _ema entry points' tail: the buffer, decay, warm-up and -- ungated -- the number of this update (st["ema_n"] counts it
+        already), gated the base of the device's count (the gate and the EMA of a group start together: 0)."""
+        return (st["ema"].data_ptr(), self.ema_decay, 1 if self.ema_warmup else 0, 0 if gated else st["ema_n"])
+
+    def ema_state(self):
+        """parameter -> its EMA (a view of the group's EMA buffer, the parameter's shape)."""
+        if self.ema_decay is None:
+            raise L.CrdError("camradepth_amd.diffGradNorm.ema_state(): the optimizer was built without ema_decay")
+        if self._groups is None:
+            self._groups = [self._build(g) for g in self.param_groups]
+        return {p: st["ema"][o:o + p.numel()].view(p.shape) for st in self._groups for p, o in zip(st["ps"], st["offs"])}
+
     def _gated_step(self, lb, group, st, ps, pbase, gptr, act_host):
         """The gated and / or clipped launches of one group (norm pass, then the commit); -> True if the step was skipped."""
         gate = self._gate(st, ps) if self.skip_nonfinite else None
@@ -191,10 +245,14 @@ class diffGradNorm(Optimizer):
             L.check(lb.crd_diffgradnorm_norm_gated(pbase, gptr, st["nsq"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(),
                                                    st["b2c"].data_ptr(), st["nblk"], active, float(group["weight_decay"]), None,
                                                    gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
-            L.check(lb.crd_diffgradnorm_commit_gated(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
-                                                     st["egn"].data_ptr(), st["nsq"].data_ptr(), st["fac"].data_ptr(), st["seg"].data_ptr(),
-                                                     st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"], active, *hyper,
-                                                     gate.data_ptr(), L.stream()), "crd_diffgradnorm_commit_gated")
+            args = (pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(), st["egn"].data_ptr(), st["nsq"].data_ptr(),
+                    st["fac"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"], active,
+                    *hyper, gate.data_ptr())
+            if st["ema"] is not None:
+                L.check(lb.crd_diffgradnorm_commit_gated_ema(*args, *self._ema_args(st, True), L.stream()),
+                        "crd_diffgradnorm_commit_gated_ema")
+            else:
+                L.check(lb.crd_diffgradnorm_commit_gated(*args, L.stream()), "crd_diffgradnorm_commit_gated")
         else:
             if st["parts"] is None:
                 st["parts"] = torch.zeros(4 * st["nblk"], dtype=torch.float32, device=ps[0].device)
@@ -203,11 +261,16 @@ class diffGradNorm(Optimizer):
             L.check(lb.crd_diffgradnorm_norm_clip(pbase, gptr, st["parts"].data_ptr(), st["nblk"], st["seg"].data_ptr(),
                                                   st["b2s"].data_ptr(), st["b2c"].data_ptr(), st["nblk"], active,
                                                   float(group["weight_decay"]), None, gp, L.stream()), "crd_diffgradnorm_norm_clip")
-            L.check(lb.crd_diffgradnorm_commit_clip(pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(),
-                                                    st["egn"].data_ptr(), st["parts"].data_ptr(), st["nblk"], st["fac"].data_ptr(),
-                                                    st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"],
-                                                    active, *hyper[:6], None, self.max_grad_norm, st["clip"].data_ptr(), gp,
-                                                    L.stream()), "crd_diffgradnorm_commit_clip")
+            args = (pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(), st["egn"].data_ptr(), st["parts"].data_ptr(),
+                    st["nblk"], st["fac"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"],
+                    active, *hyper[:6], None, self.max_grad_norm, st["clip"].data_ptr(), gp)
+            if st["ema"] is not None:
+                if gate is None:
+                    st["ema_n"] += 1
+                L.check(lb.crd_diffgradnorm_commit_clip_ema(*args, *self._ema_args(st, gate is not None), L.stream()),
+                        "crd_diffgradnorm_commit_clip_ema")
+            else:
+                L.check(lb.crd_diffgradnorm_commit_clip(*args, L.stream()), "crd_diffgradnorm_commit_clip")
             self.grad_norm = st["clip"][0].clone()        # (enqueued: no sync)
         if gate is None:
             self._count_step(st, ps, act_host)
@@ -219,6 +282,8 @@ class diffGradNorm(Optimizer):
             self.skipped_steps += 1
             return True
         self._count_step(st, ps, act_host)
+        if st["ema"] is not None:
+            st["ema_n"] += 1                 # (the device counted it itself: gate[2])
         return False
 
     def _count_step(self, st, ps, act_host):

@@ -5,6 +5,7 @@ provides -- TrainStep (HIP-graph training iteration incl. accumulation windows a
 naming (out of scope); batches may be the reference dataloader's nested dict
 (`batch["image"]`, `batch["gt"]["depth"]["lidar_depth"]`, `["lidar_depth_partial"]`, `batch["gt"]["seg"]["final_seg"]`,
 src/data/dataloader.py:320-333) or the flat dict of camradepth_amd.synth / camradepth_amd.batch."""
+import contextlib
 import math
 import time
 
@@ -14,7 +15,7 @@ from . import lib as L
 from . import losses as HL
 from .inference import InferenceGraph
 from .metrics import DepthMetrics, SegIoU
-from .optim import check_max_grad_norm
+from .optim import check_ema_decay, check_max_grad_norm
 from .trainer import TrainStep, depth_criterion_mode, one_cycle
 
 
@@ -43,7 +44,9 @@ def unpack_batch(batch, input_channels):
 class Trainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, test_dataloader=None, learning_rate=6e-5, num_epochs=1,
                  update_interval=1, div_factor=2.0, max_depth=100.0, max_distances=(100.0, 50.0), num_classes=21, group=None,
-                 use_graph=True, skip_nonfinite=False, criterion=None, max_grad_norm=None):
+                 use_graph=True, skip_nonfinite=False, criterion=None, max_grad_norm=None, ema_decay=None, ema_warmup=True,
+                 eval_with_ema=True):
+        ema_decay = check_ema_decay(ema_decay, "camradepth_amd.runner.Trainer")        # refused before anything is touched
         if model.flat is None or not model.flat.is_cuda:
             raise L.CrdError("camradepth_amd.runner.Trainer needs the model on an MI355X (no CPU fallback)")
         self.model, self.cfg = model, model.cfg
@@ -54,6 +57,10 @@ class Trainer:
         self.skip_nonfinite = skip_nonfinite          # GradScaler.step's guard (runner.py:264): TrainStep(skip_nonfinite=...)
         # clip_grad_norm_ before each optimizer step: TrainStep(max_grad_norm=...), refused here already when it is not > 0
         self.max_grad_norm = check_max_grad_norm(max_grad_norm, "camradepth_amd.runner.Trainer")
+        # EMA of the weights in the optimizer step: TrainStep(ema_decay=..., ema_warmup=...).  eval() and test() then run on the averaged
+        # weights (eval_with_ema=False: on the raw ones), so train() selects its best epoch on them
+        self.ema_decay = ema_decay
+        self.ema_warmup, self.eval_with_ema = bool(ema_warmup), bool(eval_with_ema)
         # runner.py:149; criterion = another {"depth": ..., "seg": ...} of camradepth_amd.losses (TrainStep refuses what it cannot record)
         self.criterion = criterion if criterion is not None else {"depth": HL.MaskedSmoothL1Loss(), "seg": HL.MaskedFocalLoss()}
         depth_criterion_mode(self.criterion)
@@ -77,7 +84,7 @@ class Trainer:
                                          schedule=one_cycle(max(steps, 2), self.learning_rate, div_factor=self.div_factor),
                                          use_graph=self.use_graph, group=self.group, state=self._train_state,
                                          skip_nonfinite=self.skip_nonfinite, criterion=self.criterion,
-                                         max_grad_norm=self.max_grad_norm)
+                                         max_grad_norm=self.max_grad_norm, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
             self._train_state = self._steps[key].state
         self.step = self._steps[key]
         return self.step
@@ -103,6 +110,13 @@ class Trainer:
         return {"depth_mean": _nanmean(depth), "depth_stage_4_mean": _nanmean(stage4), "RMSE": _nanmean(rmse), "seg_mean": _nanmean(seg)}
 
     # ------------------------------------------------------------------ validation (runner.py:273-350)
+    def _eval_weights(self):
+        """The context eval() / test() run in: the averaged weights when the run keeps an EMA (before the first training step it equals
+        the parameters: nothing to exchange)."""
+        if self.ema_decay is not None and self.eval_with_ema and self.step is not None:
+            return self.step.ema_weights()
+        return contextlib.nullcontext()
+
     def _forward_eval(self, image):
         B, _, H, W = image.shape
         key = (B, H, W)
@@ -116,7 +130,7 @@ class Trainer:
         self.model.eval()
         L.nonfinite()          # ... and the other way round.  The loss modules report a dropped non-finite partial as NaN
         rows = []              # (lib.stat_checked), which the nanmean below leaves out exactly like the reference's np.nanmean (runner.py:320-347)
-        with torch.no_grad():
+        with torch.no_grad(), self._eval_weights():
             for batch in self.val_dataloader:
                 b = unpack_batch(batch, self.cfg.input_channels)
                 out = self._forward_eval(b["image"])
@@ -149,7 +163,7 @@ class Trainer:
         m100, m50 = DepthMetrics(self.max_depth, self.max_distances[0]), DepthMetrics(self.max_depth, self.max_distances[0])
         iou = SegIoU(self.num_classes) if self.cfg.supervised_seg else None
         times = []
-        with torch.no_grad():
+        with torch.no_grad(), self._eval_weights():
             for batch in self.test_dataloader:
                 b = unpack_batch(batch, self.cfg.input_channels)
                 x = b["image"].cuda()

@@ -12,6 +12,7 @@ stage 2, stage 1 + patch embeds), each launched as soon as its backward segment 
 transfer overlaps the remaining backward.  The masked-mean denominators are made global first
 (one 16-float all-reduce), which reproduces the reference's loss over the gathered batch exactly.
 """
+import contextlib
 import math
 import os
 
@@ -20,7 +21,7 @@ import torch.distributed as dist
 
 from . import lib as L
 from . import trace
-from .optim import _CHUNK, check_max_grad_norm
+from .optim import _CHUNK, check_ema_decay, check_max_grad_norm, ema_weight
 
 LOSS_W = (1.0, 1.0, 1.0, 0.2, 0.2)   # runner.py:213
 
@@ -121,7 +122,8 @@ class TrainState:
     (plan, static input buffers, captured graphs); the reference's DataLoader has no drop_last (src/data/dataloader.py:40), so
     the last batch of an epoch is smaller and a second TrainStep for that shape must continue THIS state, not restart it."""
 
-    def __init__(self, model, lr, betas, eps, weight_decay, update_interval, schedule, max_grad_norm=None):
+    def __init__(self, model, lr, betas, eps, weight_decay, update_interval, schedule, max_grad_norm=None, ema_decay=None,
+                 ema_warmup=True):
         dev = model.flat.device
         n = model.flat.numel()
         self.m, self.v, self.pg = (torch.zeros(n, device=dev) for _ in range(3))
@@ -150,6 +152,12 @@ class TrainState:
         self.max_grad_norm = max_grad_norm
         self.parts = torch.zeros(4 * self.nblk, device=dev) if max_grad_norm is not None else None
         self.clip = torch.zeros(2, device=dev) if max_grad_norm is not None else None
+        # ema_decay: the exponential moving average of the parameters (layout of model.flat, seeded with them), updated by the optimizer's
+        # update kernel on every committed step.  ema_n: the updates so far as the host counts them; with skip_nonfinite the device
+        # counts (gate[2] - ema_base: TrainStep.ema_updates).  _ema_swapped: inside TrainStep.ema_weights()
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema = model.flat.detach().clone() if ema_decay is not None else None
+        self.ema_n, self.ema_base, self._ema_swapped = 0, 0, False
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.update_interval = update_interval
         self.schedule = schedule
@@ -162,7 +170,7 @@ class TrainState:
 
 _STATE_FIELDS = ("m", "v", "pg", "egn", "fac", "seg", "b2s", "b2c", "nt", "nblk", "nsq", "hp", "hp_ring", "lr", "betas", "eps", "wd",
                  "update_interval", "schedule", "iter_count", "epoch_iter", "sched_steps", "step_count", "_window_open", "_window_pos", "gate",
-                 "max_grad_norm", "parts", "clip")
+                 "max_grad_norm", "parts", "clip", "ema", "ema_decay", "ema_warmup", "ema_n", "ema_base", "_ema_swapped")
 
 
 class TrainStep:
@@ -188,12 +196,23 @@ class TrainStep:
     the weight decay is added.  The scaling happens on the fly (the flat gradient buffer keeps the unclipped values).  The global
     norm needs every bucket, so -- as with skip_nonfinite, and sharing its tail when both are on -- the buckets' late-stream
     slices only write norm parts and the commit of all of them follows the last one.  grad_norm: the window's ||g||, on the
-    device; float('inf') computes it without clipping (the bits of the default step)."""
+    device; float('inf') computes it without clipping (the bits of the default step).
+
+    ema_decay=d (0 <= d < 1): an exponential moving average of the weights, the set one evaluates and checkpoints (timm ModelEmaV2/V3,
+    torch.optim.swa_utils.AveragedModel).  `ema` is a flat fp32 buffer laid out as model.flat and seeded with the parameters; every
+    COMMITTED optimizer step n = 1, 2, ... does e <- e + w_n (p_new - e) in fp32 (one fma), w_n = 1 - d_n, d_n = min(d, (1 + n) / (10 + n))
+    with ema_warmup (timm's rule: without it d = 0.9999 averages nothing useful for the first 10^4 steps), else d.  The update
+    kernel does it where it stores the new parameter: no launch, no pass of its own, no collective (the EMA is a function of the
+    all-reduced parameters), and the training itself keeps its bits.  Frozen tensors, accumulate-only iterations and windows
+    skipped by skip_nonfinite leave it untouched.  ema_state_dict() / ema_updates read it; `with ts.ema_weights():` makes it the
+    model's weights for evaluation.  model.load_state_dict() alone does not touch the EMA (checkpoint.load_checkpoint restores or
+    re-seeds it; reseed_ema() by hand)."""
 
     def __init__(self, model, B, H, W, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, update_interval=1,
-                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False, criterion=None, max_grad_norm=None):
+                 use_graph=True, schedule=None, group=None, state=None, skip_nonfinite=False, criterion=None, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=True):
         """state: the TrainState of another TrainStep of the same model (another batch shape of the same run) to continue;
-        lr / betas / eps / weight_decay / update_interval / schedule / max_grad_norm are then taken from it."""
+        lr / betas / eps / weight_decay / update_interval / schedule / max_grad_norm / ema_decay / ema_warmup are then taken from it."""
         assert model.training, "TrainStep drives the training path: call model.train() first"
         self._depth_mode, self._berhu_thresh = depth_criterion_mode(criterion)      # refused here, before anything is allocated
         assert update_interval >= 1
@@ -203,10 +222,11 @@ class TrainStep:
                              "would poison the delayed scales")
         self.skip_nonfinite = bool(skip_nonfinite)
         max_grad_norm = check_max_grad_norm(max_grad_norm, "TrainStep")
+        ema_decay = check_ema_decay(ema_decay, "TrainStep")
         if state is not None and state.m.numel() != model.flat.numel():
             raise L.CrdError("TrainStep(state=...): the state belongs to a model with a different parameter count")
         self.state = state if state is not None else TrainState(model, lr, betas, eps, weight_decay, update_interval, schedule,
-                                                                max_grad_norm)
+                                                                max_grad_norm, ema_decay, ema_warmup)
         self.model, self.B, self.H, self.W = model, B, H, W
         self.dev = model.flat.device
         self.lib = L.load()
@@ -255,6 +275,8 @@ class TrainStep:
         if self.skip_nonfinite and self.state.gate is None:
             self.state.gate = torch.zeros(8, dtype=torch.int32, device=self.dev)
             self.state.gate[2] = self.state.step_count          # committed steps so far (a continued TrainState)
+            if getattr(self.state, "ema", None) is not None:
+                self.state.ema_base = self.state.step_count - self.state.ema_n
 
     # ------------------------------------------------------------------ skip_nonfinite: what the device decided (one sync per read)
     @property
@@ -276,6 +298,58 @@ class TrainStep:
         """max_grad_norm: ||g|| of the last closed accumulation window before clipping (clip_grad_norm_'s return value), a 0-d fp32
         device tensor taken in stream order (no sync); None without max_grad_norm."""
         return None if self.clip is None else self.clip[0].clone()
+
+    # ------------------------------------------------------------------ ema_decay: the averaged weights
+    @property
+    def ema_updates(self):
+        """EMA updates since it was created or restored = the optimizer steps committed since then (skip_nonfinite: read from the
+        device, one sync, as committed_steps); None without ema_decay."""
+        if getattr(self, "ema", None) is None:
+            return None
+        return self.ema_n if self.gate is None else int(self.gate[2]) - self.ema_base
+
+    def ema_state_dict(self):
+        """name -> view of the EMA buffer, with model.state_dict()'s keys and shapes (inside ema_weights() the buffers are
+        exchanged: this is then the raw weights' dict)."""
+        if self.ema is None:
+            raise L.CrdError("TrainStep.ema_state_dict(): the step was built without ema_decay")
+        return {name: self.ema[a:b].view(self.model._param(name).shape) for name, (a, b) in zip(self.model._names, self.state.seg_host)}
+
+    def reseed_ema(self, updates=0):
+        """EMA <- the current parameters, with `updates` as the count the warm-up continues from (a restart from weights alone)."""
+        if self.ema is None:
+            raise L.CrdError("TrainStep.reseed_ema(): the step was built without ema_decay")
+        self.ema.copy_(self.model.flat.detach())
+        self._set_ema_updates(updates)
+
+    def _set_ema_updates(self, n):
+        self.ema_n = int(n)
+        self.ema_base = self.committed_steps - self.ema_n
+
+    def _swap_ema(self):
+        L.check(self.lib.crd_swap_f32(self.model.flat.data_ptr(), self.ema.data_ptr(), self.ema.numel(), L.stream()), "crd_swap_f32")
+        self.model.mark_params_changed()       # TrainStep / InferenceGraph re-pack (and re-quantise fp8 weights) before their next replay
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters ARE the averaged weights (and `ema` holds the raw ones): model.forward,
+        InferenceGraph, state_dict() and save_checkpoint see them.  An in-place exchange of the two flat buffers (crd_swap_f32, no
+        temporary) and back on exit, so the raw bits are restored exactly.  step() refuses to run inside; not re-entrant."""
+        if self.ema is None:
+            raise L.CrdError("TrainStep.ema_weights(): the step was built without ema_decay")
+        if self._ema_swapped:
+            raise L.CrdError("TrainStep.ema_weights() is not re-entrant: the averaged weights are already in place")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False
+
+    def _ema_args(self, gated):
+        """The _ema entry points' tail arguments.  Under hp (always, here) the kernels read w_n / decay / base / warm-up from it."""
+        return (self.ema.data_ptr(), self.ema_decay, 1 if self.ema_warmup else 0, self.ema_base if gated else 0)
 
     def optimizer_state(self):
         """diffGradNorm's state in the reference's per-parameter form (diffGradNorm.py:63-71), with `step` = committed steps: what
@@ -358,12 +432,14 @@ class TrainStep:
         """key: only the tensors of that gradient bucket (block-table slice + `active` mask)."""
         m = self.model
         b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
-        L.check(self.lib.crd_diffgradnorm_step(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                               self.pg.data_ptr(), self.egn.data_ptr(), self.nsq.data_ptr() + 4 * b0, self.fac.data_ptr(),
-                                               self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0, self.b2c.data_ptr() + 4 * b0,
-                                               self.nt, nb, None if mask is None else mask.data_ptr(),
-                                               0.0, 0.0, 0.0, 0.0, 0.0, 1, self.hp.data_ptr(), L.stream()),
-                "crd_diffgradnorm_step")
+        args = (m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.pg.data_ptr(), self.egn.data_ptr(),
+                self.nsq.data_ptr() + 4 * b0, self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0,
+                self.b2c.data_ptr() + 4 * b0, self.nt, nb, None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1,
+                self.hp.data_ptr())
+        if getattr(self, "ema", None) is not None:         # the update kernel's EMA instantiation: the same launches
+            L.check(self.lib.crd_diffgradnorm_step_ema(*args, *self._ema_args(False), L.stream()), "crd_diffgradnorm_step_ema")
+        else:
+            L.check(self.lib.crd_diffgradnorm_step(*args, L.stream()), "crd_diffgradnorm_step")
         # the bucket's new weights in the kernels' bf16 layouts, right behind its update (late stream: under the encoder's
         # backward) instead of one 169-us launch at the head of the next forward
         lo, hi = (None, None) if key is None else self.sync.ranges[key]
@@ -385,12 +461,13 @@ class TrainStep:
         """Every tensor's scalar and update, or none of them, then the re-pack of all weights (of unchanged ones after a skip: the
         packed forms are a function of the fp32 parameters, so re-packing them writes the same bits)."""
         m, mask = self.model, self.trainable_mask
-        L.check(self.lib.crd_diffgradnorm_commit_gated(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                       self.pg.data_ptr(), self.egn.data_ptr(), self.nsq.data_ptr(), self.fac.data_ptr(),
-                                                       self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(), self.nt, self.nblk,
-                                                       None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1,
-                                                       self.hp.data_ptr(), self.gate.data_ptr(), L.stream()),
-                "crd_diffgradnorm_commit_gated")
+        args = (m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.pg.data_ptr(), self.egn.data_ptr(),
+                self.nsq.data_ptr(), self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(), self.nt, self.nblk,
+                None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1, self.hp.data_ptr(), self.gate.data_ptr())
+        if getattr(self, "ema", None) is not None:
+            L.check(self.lib.crd_diffgradnorm_commit_gated_ema(*args, *self._ema_args(True), L.stream()), "crd_diffgradnorm_commit_gated_ema")
+        else:
+            L.check(self.lib.crd_diffgradnorm_commit_gated(*args, L.stream()), "crd_diffgradnorm_commit_gated")
         self.plan.pack()
 
     # max_grad_norm pieces: the norm pass that also writes the parts of the global norm (per bucket or all; gated with
@@ -406,13 +483,15 @@ class TrainStep:
 
     def _commit_clip(self):
         m, mask = self.model, self.trainable_mask
-        L.check(self.lib.crd_diffgradnorm_commit_clip(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                      self.pg.data_ptr(), self.egn.data_ptr(), self.parts.data_ptr(), self.nblk,
-                                                      self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(),
-                                                      self.nt, self.nblk, None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0,
-                                                      0.0, 1, self.hp.data_ptr(), self.max_grad_norm, self.clip.data_ptr(),
-                                                      self.gate.data_ptr() if self.skip_nonfinite else None, L.stream()),
-                "crd_diffgradnorm_commit_clip")
+        args = (m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.pg.data_ptr(), self.egn.data_ptr(),
+                self.parts.data_ptr(), self.nblk, self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(),
+                self.nt, self.nblk, None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1, self.hp.data_ptr(),
+                self.max_grad_norm, self.clip.data_ptr(), self.gate.data_ptr() if self.skip_nonfinite else None)
+        if getattr(self, "ema", None) is not None:
+            L.check(self.lib.crd_diffgradnorm_commit_clip_ema(*args, *self._ema_args(self.skip_nonfinite), L.stream()),
+                    "crd_diffgradnorm_commit_clip_ema")
+        else:
+            L.check(self.lib.crd_diffgradnorm_commit_clip(*args, L.stream()), "crd_diffgradnorm_commit_clip")
         self.plan.pack()
 
     def _deferred(self):
@@ -472,7 +551,8 @@ class TrainStep:
         changes is restored afterwards."""
         self.plan.ensure_packed()
         keep = (self.model.flat, self.m, self.v, self.pg, self.egn, self.nsq, self.fac, self.model.flat_grad) + \
-            ((self.gate,) if self.skip_nonfinite else ()) + ((self.parts, self.clip) if self.max_grad_norm is not None else ())
+            ((self.gate,) if self.skip_nonfinite else ()) + ((self.parts, self.clip) if self.max_grad_norm is not None else ()) + \
+            ((self.ema,) if self.ema is not None else ())
         saved = [t.clone() for t in keep]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -651,6 +731,10 @@ class TrainStep:
         if tuple(p.requires_grad for p in self._params) != self._frozen_sig:
             raise L.CrdError("camradepth_amd.TrainStep: requires_grad of a parameter changed after the step was built (its plan "
                              "and optimizer mask are fixed at construction): build a new TrainStep")
+        ema = getattr(self, "ema", None) is not None
+        if ema and self._ema_swapped:
+            raise L.CrdError("camradepth_amd.TrainStep.step() inside ema_weights(): the parameters are the averaged weights there; "
+                             "leave the context before training on")
         k = self.update_interval
         zero = not self._window_open             # first iteration of an accumulation window: zero the gradients
         pos = self._window_pos if self._window_open else 0
@@ -664,6 +748,13 @@ class TrainStep:
             hp_host = self.hp_ring[self.step_count % len(self.hp_ring)]   # ring: the async copy may still be pending
             hp_host[0], hp_host[1], hp_host[2], hp_host[3] = b1, b2, self.eps, self.wd
             hp_host[4] = lr * math.sqrt(bc2) / (bc1 + 1e-8)
+            if ema:
+                # [5] w_n of this update as the host counts it (the ungated kernels); [6], [7], [15]: decay, base and warm-up, from
+                # which the gated commit forms w_n for the device's own count (include/camradepth_hip.h, crd_diffgradnorm_*_ema)
+                if not getattr(self, "skip_nonfinite", False):
+                    self.ema_n += 1
+                hp_host[5], hp_host[6] = ema_weight(self.ema_decay, self.ema_warmup, max(self.ema_n, 1))[1], self.ema_decay
+                hp_host.view(torch.int32)[7], hp_host.view(torch.int32)[15] = self.ema_base, 1 if self.ema_warmup else 0
             if getattr(self, "skip_nonfinite", False):
                 hp_host.view(torch.float64)[4:7] = torch.tensor([lr, b1, b2], dtype=torch.float64)
                 hp_host.view(torch.int32)[14] = self.step_count

@@ -64,7 +64,7 @@ int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
 int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 8        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 9        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -714,6 +714,38 @@ int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float
                                  int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
                                  float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
                                  int32_t* gate, crd_stream_t stream);
+/* ema_decay: the three commit paths above with an exponential moving average of the parameters updated in the same pass.  ema:
+ * device fp32 buffer with the layout of p.  For every element the update kernel writes (active tensors of a committed step only),
+ * in fp32:   d_n = ema_warmup ? fminf(ema_decay, (float)(1 + n) / (float)(10 + n)) : ema_decay;   w_n = 1.0f - d_n;
+ *            ema = fmaf(w_n, p_new - ema, ema)          (p_new: the value stored to p; 0 <= ema_decay < 1)
+ * n = 1, 2, ... counts the committed steps since the EMA was created or restored.  Without a gate the host knows it: ema_n = n, or
+ * with hp_dev the host leaves w_n itself in hp_dev[5] (ema_n is then ignored), so a captured graph follows n without re-capture.
+ * With a gate only the device knows which steps were committed: n = gate[2] (after this step's verdict) - ema_base, w_n is formed
+ * on the device by the expression above; with hp_dev, ema_decay / ema_base / ema_warmup are read from hp_dev[6], the int32 at
+ * hp_dev[7] and the int32 at hp_dev[15].  crd_diffgradnorm_commit_clip_ema: ema_n is n without a gate, ema_base with one.
+ * Everything else -- p, the optimizer state, the status codes -- is what the entry point without _ema does, bit for bit. */
+int crd_diffgradnorm_step_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                              float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
+                              const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                              const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                              int32_t step, const float* hp_dev, float* ema, float ema_decay, int32_t ema_warmup, int32_t ema_n,
+                              crd_stream_t stream);
+int crd_diffgradnorm_commit_gated_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                      float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
+                                      const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
+                                      const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      int32_t step, const float* hp_dev, int32_t* gate, float* ema, float ema_decay,
+                                      int32_t ema_warmup, int32_t ema_base, crd_stream_t stream);
+int crd_diffgradnorm_commit_clip_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
+                                     float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
+                                     const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
+                                     int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
+                                     float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
+                                     int32_t* gate, float* ema, float ema_decay, int32_t ema_warmup, int32_t ema_n,
+                                     crd_stream_t stream);
+/* a[i] <-> b[i] for i < n, in place (no temporary): two fp32 buffers that do not overlap, any 4-byte alignment (16-byte loads and
+ * stores where both buffers allow them, single elements at the ends); n = 0 does nothing.  Exchanges the parameters with their EMA. */
+int crd_swap_f32(float* a, float* b, int64_t n, crd_stream_t stream);
 
 #ifdef __cplusplus
 }
