@@ -614,199 +614,98 @@ extern "C" int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int3
   return CRD_OK;
 }
 
-// One body per commit path; `ema` = nullptr launches today's instantiation of the update (the entry points without _ema)
-static int dgn_step(const char* who, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad, float* exp_grad_norm,
-                    float* norm_sq, float* factor, const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk,
-                    int32_t n_tensors, int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
-                    float weight_decay, int32_t step, const float* hp_dev, const DgnEma* ema, crd_stream_t stream) {
-  hipStream_t st = as_stream(stream);
-  const long long* so = reinterpret_cast<const long long*>(seg_off);
-  hipLaunchKernelGGL(k_dgn_norm<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, so, blk2seg, blk2chunk, weight_decay, hp_dev, norm_sq, active,
-                     nullptr);
-  hipLaunchKernelGGL(k_dgn_scalar<false>, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so,
-                     blk2seg, n_blocks, nullptr, nullptr, DgnGateHost{0.f, 0});
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
-  if (ema)
-    hipLaunchKernelGGL((k_dgn_update<false, false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, nullptr, *ema);
-  else
-    hipLaunchKernelGGL(k_dgn_update<false>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
-                       blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr);
-  CRD_LAUNCH_CHECK(who);
-  return CRD_OK;
+// ---- diffGradNorm: crd_dgn_desc (include/camradepth_hip.h).  The switches are gate / clip / ema != NULL; the kernels take them as
+// template flags, and dgn_norm / dgn_commit below are the only places that map the one onto the other. ----
+template <bool GATED, bool CLIP>
+static void dgn_norm_launch(const crd_dgn_desc& d, hipStream_t st) {
+  hipLaunchKernelGGL((k_dgn_norm<GATED, CLIP>), dim3(d.n_blocks), dim3(TPB), 0, st, d.p, d.g, reinterpret_cast<const long long*>(d.seg_off),
+                     d.blk2seg, d.blk2chunk, d.weight_decay, d.hp_dev, d.parts, d.active, d.gate, (long long)d.parts_stride);
 }
-
-#define DGN_EMA_ARGS_OK(e, d, n) ((e) && (d) >= 0.f && (d) < 1.f && (n) >= 0)
-
-extern "C" int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                     float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
-                                     const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                     const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                     int32_t step, const float* hp_dev, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
-                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1,
-                "crd_diffgradnorm_step: bad argument");
-  return dgn_step("crd_diffgradnorm_step", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off, blk2seg, blk2chunk,
-                  n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, nullptr, stream);
-}
-
-extern "C" int crd_diffgradnorm_step_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                         float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
-                                         const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                         const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                         int32_t step, const float* hp_dev, float* ema, float ema_decay, int32_t ema_warmup,
-                                         int32_t ema_n, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
-                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && DGN_EMA_ARGS_OK(ema, ema_decay, ema_n) && (hp_dev || ema_n >= 1),
-                "crd_diffgradnorm_step_ema: bad argument");
-  const DgnEma ea{ema, dgn_ema_weight(ema_decay, ema_warmup, ema_n), ema_decay, ema_warmup, 0};
-  return dgn_step("crd_diffgradnorm_step_ema", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off, blk2seg,
-                  blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, &ea, stream);
-}
-
-// ---- gated diffGradNorm (skip_nonfinite): include/camradepth_hip.h ----
-extern "C" int crd_diffgradnorm_norm_gated(const float* p, const float* g, float* norm_sq, const int64_t* seg_off, const int32_t* blk2seg,
-                                           const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active, float weight_decay,
-                                           const float* hp_dev, int32_t* gate, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && norm_sq && seg_off && blk2seg && blk2chunk && n_blocks > 0 && gate, "crd_diffgradnorm_norm_gated: bad argument");
-  hipLaunchKernelGGL(k_dgn_norm<true>, dim3(n_blocks), dim3(TPB), 0, as_stream(stream), p, g, reinterpret_cast<const long long*>(seg_off),
-                     blk2seg, blk2chunk, weight_decay, hp_dev, norm_sq, active, gate);
-  CRD_LAUNCH_CHECK("crd_diffgradnorm_norm_gated");
-  return CRD_OK;
-}
-
-static int dgn_commit_gated(const char* who, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                            float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off, const int32_t* blk2seg,
-                            const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks, const uint8_t* active, float lr, float beta1,
-                            float beta2, float eps, float weight_decay, int32_t step, const float* hp_dev, int32_t* gate,
-                            const DgnEma* ema, crd_stream_t stream) {
-  hipStream_t st = as_stream(stream);
-  const long long* so = reinterpret_cast<const long long*>(seg_off);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
-  hipLaunchKernelGGL(k_dgn_scalar<true>, dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, norm_sq, factor, active, n_tensors, so,
-                     blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step});
-  if (ema)
-    hipLaunchKernelGGL((k_dgn_update<true, false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                       blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, nullptr, *ema);
-  else
-    hipLaunchKernelGGL(k_dgn_update<true>, dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so, blk2seg,
-                       blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, gate);
-  CRD_LAUNCH_CHECK(who);
-  return CRD_OK;
-}
-
-extern "C" int crd_diffgradnorm_commit_gated(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                             float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
-                                             const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                             const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                             int32_t step, const float* hp_dev, int32_t* gate, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
-                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && gate,
-                "crd_diffgradnorm_commit_gated: bad argument");
-  return dgn_commit_gated("crd_diffgradnorm_commit_gated", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off,
-                          blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, gate, nullptr,
-                          stream);
-}
-
-extern "C" int crd_diffgradnorm_commit_gated_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                                 float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
-                                                 const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                                 const uint8_t* active, float lr, float beta1, float beta2, float eps,
-                                                 float weight_decay, int32_t step, const float* hp_dev, int32_t* gate, float* ema,
-                                                 float ema_decay, int32_t ema_warmup, int32_t ema_base, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && norm_sq && factor && seg_off && blk2seg &&
-                    blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && gate && DGN_EMA_ARGS_OK(ema, ema_decay, ema_base),
-                "crd_diffgradnorm_commit_gated_ema: bad argument");
-  const DgnEma ea{ema, 0.f, ema_decay, ema_warmup, ema_base};
-  return dgn_commit_gated("crd_diffgradnorm_commit_gated_ema", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, norm_sq, factor, seg_off,
-                          blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev, gate, &ea,
-                          stream);
-}
-
-// ---- diffGradNorm with global gradient-norm clipping (max_grad_norm): include/camradepth_hip.h ----
-extern "C" int crd_diffgradnorm_norm_clip(const float* p, const float* g, float* parts, int64_t parts_stride, const int64_t* seg_off,
-                                          const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active,
-                                          float weight_decay, const float* hp_dev, int32_t* gate, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && parts && parts_stride >= n_blocks && seg_off && blk2seg && blk2chunk && n_blocks > 0,
-                "crd_diffgradnorm_norm_clip: bad argument");
-  const long long* so = reinterpret_cast<const long long*>(seg_off);
-  if (gate)
-    hipLaunchKernelGGL((k_dgn_norm<true, true>), dim3(n_blocks), dim3(TPB), 0, as_stream(stream), p, g, so, blk2seg, blk2chunk, weight_decay,
-                       hp_dev, parts, active, gate, (long long)parts_stride);
-  else
-    hipLaunchKernelGGL((k_dgn_norm<false, true>), dim3(n_blocks), dim3(TPB), 0, as_stream(stream), p, g, so, blk2seg, blk2chunk,
-                       weight_decay, hp_dev, parts, active, nullptr, (long long)parts_stride);
-  CRD_LAUNCH_CHECK("crd_diffgradnorm_norm_clip");
-  return CRD_OK;
-}
-
-static int dgn_commit_clip(const char* who, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                           float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor, const int64_t* seg_off,
-                           const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks, const uint8_t* active,
-                           float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* hp_dev,
-                           float max_norm, float* clip, int32_t* gate, const DgnEma* ema, crd_stream_t stream) {
-  hipStream_t st = as_stream(stream);
-  const long long* so = reinterpret_cast<const long long*>(seg_off);
-  const long long ps = parts_stride;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr * sqrt(bc2) / (bc1 + 1e-8));
-  hipLaunchKernelGGL(k_grad_norm_total, dim3(1), dim3(256), 0, st, parts + ps, n_blocks, max_norm, clip);
-  if (gate) {
-    hipLaunchKernelGGL((k_dgn_scalar<true, true>), dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, parts, factor, active, n_tensors,
-                       so, blk2seg, n_blocks, gate, hp_dev, DgnGateHost{step_size, step}, weight_decay, (const float*)clip, ps);
-    if (ema)
-      hipLaunchKernelGGL((k_dgn_update<true, true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, (const float*)clip,
-                         *ema);
-    else
-      hipLaunchKernelGGL((k_dgn_update<true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, (const int*)gate, (const float*)clip);
-  } else {
-    hipLaunchKernelGGL((k_dgn_scalar<false, true>), dim3(cdiv(n_tensors, 4)), dim3(256), 0, st, exp_grad_norm, parts, factor, active,
-                       n_tensors, so, blk2seg, n_blocks, nullptr, hp_dev, DgnGateHost{0.f, 0}, weight_decay, (const float*)clip, ps);
-    if (ema)
-      hipLaunchKernelGGL((k_dgn_update<false, true, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, (const float*)clip, *ema);
-    else
-      hipLaunchKernelGGL((k_dgn_update<false, true>), dim3(n_blocks), dim3(TPB), 0, st, p, g, exp_avg, exp_avg_sq, prev_grad, factor, so,
-                         blk2seg, blk2chunk, active, beta1, beta2, eps, weight_decay, step_size, hp_dev, nullptr, (const float*)clip);
+static void dgn_norm(const crd_dgn_desc& d, hipStream_t st) {
+  switch ((d.gate ? 2 : 0) | (d.clip ? 1 : 0)) {
+    case 0: dgn_norm_launch<false, false>(d, st); break;
+    case 1: dgn_norm_launch<false, true>(d, st); break;
+    case 2: dgn_norm_launch<true, false>(d, st); break;
+    default: dgn_norm_launch<true, true>(d, st); break;
   }
-  CRD_LAUNCH_CHECK(who);
+}
+
+// [total + coefficient,] the per-tensor scalars, the update.  Arguments an instantiation does not read (gate, clip, the EMA,
+// hp in the plain scalar kernel) are passed as they are in the descriptor.
+template <bool GATED, bool CLIP, bool EMA>
+static void dgn_commit_launch(const crd_dgn_desc& d, float step_size, const DgnEma& ea, hipStream_t st) {
+  const long long* so = reinterpret_cast<const long long*>(d.seg_off);
+  const long long ps = d.parts_stride;
+  if (CLIP) hipLaunchKernelGGL(k_grad_norm_total, dim3(1), dim3(256), 0, st, d.parts + ps, d.n_blocks, d.max_norm, d.clip);
+  hipLaunchKernelGGL((k_dgn_scalar<GATED, CLIP>), dim3(cdiv(d.n_tensors, 4)), dim3(256), 0, st, d.exp_grad_norm, d.parts, d.factor, d.active,
+                     d.n_tensors, so, d.blk2seg, d.n_blocks, d.gate, d.hp_dev, DgnGateHost{step_size, d.step}, d.weight_decay,
+                     (const float*)d.clip, ps);
+  hipLaunchKernelGGL((k_dgn_update<GATED, CLIP, EMA>), dim3(d.n_blocks), dim3(TPB), 0, st, d.p, d.g, d.exp_avg, d.exp_avg_sq, d.prev_grad,
+                     d.factor, so, d.blk2seg, d.blk2chunk, d.active, d.beta1, d.beta2, d.eps, d.weight_decay, step_size, d.hp_dev,
+                     (const int*)d.gate, (const float*)d.clip, ea);
+}
+static void dgn_commit(const crd_dgn_desc& d, hipStream_t st) {
+  const double bc1 = 1.0 - pow((double)d.beta1, (double)d.step), bc2 = 1.0 - pow((double)d.beta2, (double)d.step);
+  const float step_size = (float)((double)d.lr * sqrt(bc2) / (bc1 + 1e-8));
+  // without a gate the host forms w_n (read when hp_dev is NULL); with one the device forms it from its own count and the base
+  DgnEma ea{};
+  if (d.ema) ea = DgnEma{d.ema, d.gate ? 0.f : dgn_ema_weight(d.ema_decay, d.ema_warmup, d.ema_n), d.ema_decay, d.ema_warmup,
+                         d.gate ? d.ema_base : 0};
+  switch ((d.gate ? 4 : 0) | (d.clip ? 2 : 0) | (d.ema ? 1 : 0)) {
+    case 0: dgn_commit_launch<false, false, false>(d, step_size, ea, st); break;
+    case 1: dgn_commit_launch<false, false, true>(d, step_size, ea, st); break;
+    case 2: dgn_commit_launch<false, true, false>(d, step_size, ea, st); break;
+    case 3: dgn_commit_launch<false, true, true>(d, step_size, ea, st); break;
+    case 4: dgn_commit_launch<true, false, false>(d, step_size, ea, st); break;
+    case 5: dgn_commit_launch<true, false, true>(d, step_size, ea, st); break;
+    case 6: dgn_commit_launch<true, true, false>(d, step_size, ea, st); break;
+    default: dgn_commit_launch<true, true, true>(d, step_size, ea, st); break;
+  }
+}
+
+// The argument checks of all three entry points, before any launch.  commit = false: the norm pass alone, which reads nothing more
+// than what the first two checks cover.
+static int dgn_check(const char* who, const crd_dgn_desc* d, bool commit) {
+  CRD_CHECK_ARG(d, "%s: null descriptor", who);
+  CRD_CHECK_ARG(d->p && d->g && d->parts && d->seg_off && d->blk2seg && d->blk2chunk && d->n_blocks > 0,
+                "%s: bad argument (p, g, parts or a table is null, or n_blocks <= 0)", who);
+  if (d->clip) CRD_CHECK_ARG(d->parts_stride >= d->n_blocks, "%s: bad argument (clip: parts_stride < n_blocks)", who);
+  if (!commit) return CRD_OK;
+  CRD_CHECK_ARG(d->exp_avg && d->exp_avg_sq && d->prev_grad && d->exp_grad_norm && d->factor && d->n_tensors > 0 && d->step >= 1,
+                "%s: bad argument (an optimizer-state buffer is null, n_tensors <= 0 or step < 1)", who);
+  if (d->clip) {
+    CRD_CHECK_ARG(d->max_norm > 0.f, "%s: bad argument (clip: max_norm must be > 0)", who);
+    // k_grad_norm_total adds row 1 over n_blocks: a commit over a slice of the blocks would clip with a partial norm
+    CRD_CHECK_ARG(d->parts_stride == d->n_blocks, "%s: bad argument (clip: the commit takes all blocks, parts_stride == n_blocks)", who);
+  }
+  if (d->ema) {
+    CRD_CHECK_ARG(d->ema_decay >= 0.f && d->ema_decay < 1.f, "%s: bad argument (ema: 0 <= ema_decay < 1)", who);
+    if (d->gate) CRD_CHECK_ARG(d->ema_base >= 0, "%s: bad argument (ema with a gate: ema_base < 0)", who);
+    else CRD_CHECK_ARG(d->ema_n >= (d->hp_dev ? 0 : 1), "%s: bad argument (ema without a gate: ema_n < 1)", who);
+  }
   return CRD_OK;
 }
 
-extern "C" int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                            float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
-                                            const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
-                                            int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
-                                            float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
-                                            int32_t* gate, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && parts && parts_stride >= n_blocks && factor && seg_off &&
-                    blk2seg && blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && max_norm > 0.f && clip,
-                "crd_diffgradnorm_commit_clip: bad argument");
-  return dgn_commit_clip("crd_diffgradnorm_commit_clip", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, parts, parts_stride, factor,
-                         seg_off, blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step, hp_dev,
-                         max_norm, clip, gate, nullptr, stream);
+extern "C" int crd_diffgradnorm_norm(const crd_dgn_desc* d, crd_stream_t stream) {
+  if (int rc = dgn_check("crd_diffgradnorm_norm", d, false)) return rc;
+  dgn_norm(*d, as_stream(stream));
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_norm");
+  return CRD_OK;
 }
 
-extern "C" int crd_diffgradnorm_commit_clip_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                                float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
-                                                const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk,
-                                                int32_t n_tensors, int32_t n_blocks, const uint8_t* active, float lr, float beta1,
-                                                float beta2, float eps, float weight_decay, int32_t step, const float* hp_dev,
-                                                float max_norm, float* clip, int32_t* gate, float* ema, float ema_decay,
-                                                int32_t ema_warmup, int32_t ema_n, crd_stream_t stream) {
-  CRD_CHECK_ARG(p && g && exp_avg && exp_avg_sq && prev_grad && exp_grad_norm && parts && parts_stride >= n_blocks && factor && seg_off &&
-                    blk2seg && blk2chunk && n_tensors > 0 && n_blocks > 0 && step >= 1 && max_norm > 0.f && clip &&
-                    DGN_EMA_ARGS_OK(ema, ema_decay, ema_n) && (gate || hp_dev || ema_n >= 1),
-                "crd_diffgradnorm_commit_clip_ema: bad argument");
-  // ema_n: without a gate the number n of this EMA update, with one the base of crd_diffgradnorm_commit_gated_ema
-  const DgnEma ea{ema, gate ? 0.f : dgn_ema_weight(ema_decay, ema_warmup, ema_n), ema_decay, ema_warmup, gate ? ema_n : 0};
-  return dgn_commit_clip("crd_diffgradnorm_commit_clip_ema", p, g, exp_avg, exp_avg_sq, prev_grad, exp_grad_norm, parts, parts_stride,
-                         factor, seg_off, blk2seg, blk2chunk, n_tensors, n_blocks, active, lr, beta1, beta2, eps, weight_decay, step,
-                         hp_dev, max_norm, clip, gate, &ea, stream);
+extern "C" int crd_diffgradnorm_commit(const crd_dgn_desc* d, crd_stream_t stream) {
+  if (int rc = dgn_check("crd_diffgradnorm_commit", d, true)) return rc;
+  dgn_commit(*d, as_stream(stream));
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_commit");
+  return CRD_OK;
+}
+
+extern "C" int crd_diffgradnorm_step(const crd_dgn_desc* d, crd_stream_t stream) {
+  if (int rc = dgn_check("crd_diffgradnorm_step", d, true)) return rc;
+  dgn_norm(*d, as_stream(stream));
+  dgn_commit(*d, as_stream(stream));
+  CRD_LAUNCH_CHECK("crd_diffgradnorm_step");
+  return CRD_OK;
 }
 
 extern "C" int crd_swap_f32(float* a, float* b, int64_t n, crd_stream_t stream) {

@@ -89,8 +89,17 @@ class UnpackEntry(C.Structure):
     ]
 
 
+class DgnDesc(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("p", "g", "exp_avg", "exp_avg_sq", "prev_grad", "exp_grad_norm", "factor", "parts", "seg_off",
+                                          "blk2seg", "blk2chunk", "active", "hp_dev", "gate", "clip", "ema")] + \
+               [("parts_stride", C.c_int64), ("n_tensors", C.c_int32), ("n_blocks", C.c_int32)] + \
+               [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + \
+               [("step", C.c_int32), ("max_norm", C.c_float), ("ema_decay", C.c_float),
+                ("ema_warmup", C.c_int32), ("ema_n", C.c_int32), ("ema_base", C.c_int32)]
+
+
 _lib = None
-ABI_VERSION = 9          # include/camradepth_hip.h: CRD_ABI_VERSION
+ABI_VERSION = 10         # include/camradepth_hip.h: CRD_ABI_VERSION
 
 
 def load():
@@ -146,13 +155,10 @@ _SIGS = {
     "crd_ce_focal_bwd": "ppiilppfpp",
     "crd_masked_dist_fwd": "pplpp", "crd_masked_dist_bwd": "pplppfipp", "crd_masked_berhu_max": "pplppp",
     "crd_masked_berhu": "pplppLppfpp", "crd_smoothness_fwd": "ppiiiipp", "crd_smoothness_bwd": "ppiiiippfpp",
-    "crd_diffgradnorm_step": "pppppppppppiipfffffipp",
+    "crd_diffgradnorm_norm": "pp", "crd_diffgradnorm_commit": "pp", "crd_diffgradnorm_step": "pp",
     "crd_mlp_fused_supported": "iiii", "crd_mlp_fwd": "pp", "crd_mlp_reduce": "pipppiiipppp",
     "crd_nonfinite_status": "ip", "crd_nonfinite_capture": "pp",
-    "crd_diffgradnorm_norm_gated": "ppppppipfppp", "crd_diffgradnorm_commit_gated": "pppppppppppiipfffffippp",
-    "crd_diffgradnorm_norm_clip": "ppplpppipfppp", "crd_diffgradnorm_commit_clip": "ppppppplppppiipfffffipfppp",
-    "crd_diffgradnorm_step_ema": "pppppppppppiipfffffippfiip", "crd_diffgradnorm_commit_gated_ema": "pppppppppppiipfffffipppfiip",
-    "crd_diffgradnorm_commit_clip_ema": "ppppppplppppiipfffffipfpppfiip", "crd_swap_f32": "pplp",
+    "crd_swap_f32": "pplp",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "L": C.c_uint64, "f": C.c_float}
 EXPORTS = list(_SIGS)

@@ -4,6 +4,8 @@ Same constructor, `param_groups` and per-parameter `state` keys as the reference
 (src/models/diffGradNorm.py:26-37,63-71) so `OneCycleLR(cycle_momentum=True)` can drive `lr` and
 `betas[0]` every iteration (src/main/runner.py:151-152,270) and optimizer state_dicts interchange.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 from torch.optim.optimizer import Optimizer
@@ -47,6 +49,18 @@ def ema_weight(decay, warmup, n):
     if warmup:
         d = min(d, np.float32(1 + n) / np.float32(10 + n))
     return float(d), float(np.float32(1.0) - d)
+
+
+def dgn_desc(**fields):
+    """crd_dgn_desc (include/camradepth_hip.h) from named values.  A tensor stands for its device address (an int is taken as an
+    address already: a slice that starts inside a buffer); fields left out are 0 / NULL, step is 1.  gate / clip / ema = None switch
+    the feature off."""
+    d = L.DgnDesc(step=1)
+    for k, v in fields.items():
+        if not hasattr(L.DgnDesc, k):
+            raise TypeError(f"crd_dgn_desc has no field {k!r}")
+        setattr(d, k, v.data_ptr() if torch.is_tensor(v) else v)
+    return d
 
 
 class diffGradNorm(Optimizer):
@@ -195,24 +209,36 @@ class diffGradNorm(Optimizer):
                 st["active"].copy_(torch.tensor(act_host, dtype=torch.uint8))
                 st["act_host"] = None
             beta1, beta2 = group["betas"]
-            pbase = st["flat_p"].data_ptr() if st["flat_p"] is not None else st["base"]
-            if self.skip_nonfinite or self.max_grad_norm is not None:
-                if not self._gated_step(lb, group, st, ps, pbase, gptr, act_host):
-                    self._mark_changed(ps)
-                continue
-            st["step"] += 1
-            args = (pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(), st["egn"].data_ptr(), st["nsq"].data_ptr(),
-                    st["fac"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"],
-                    None if all(act_host) else st["active"].data_ptr(), float(group["lr"]), float(beta1), float(beta2),
-                    float(group["eps"]), float(group["weight_decay"]), st["step"], None)
-            if st["ema"] is not None:
+            # one call whatever the switches: norm pass, then the commit.  skip_nonfinite: the verdict words; max_grad_norm: 4 rows of
+            # norm parts and [total, coef]; ema_decay: ungated the host numbers the update, gated the device counts (gate[2], base 0:
+            # the gate and the EMA of a group start together)
+            gate = self._gate(st, ps) if self.skip_nonfinite else None
+            clipped = self.max_grad_norm is not None
+            if clipped and st["parts"] is None:
+                st["parts"] = torch.zeros(4 * st["nblk"], dtype=torch.float32, device=ps[0].device)
+                st["clip"] = torch.zeros(2, dtype=torch.float32, device=ps[0].device)
+            if st["ema"] is not None and gate is None:
                 st["ema_n"] += 1
-                L.check(lb.crd_diffgradnorm_step_ema(*args, *self._ema_args(st, False), L.stream()), "crd_diffgradnorm_step_ema")
-            else:
-                L.check(lb.crd_diffgradnorm_step(*args, L.stream()), "crd_diffgradnorm_step")
-            for p, a_ in zip(ps, act_host):
-                if a_:
-                    self.state[p]["step"] += 1
+            d = dgn_desc(p=st["flat_p"] if st["flat_p"] is not None else st["base"], g=gptr, exp_avg=st["m"], exp_avg_sq=st["v"],
+                         prev_grad=st["pg"], exp_grad_norm=st["egn"], factor=st["fac"], parts=st["parts"] if clipped else st["nsq"],
+                         parts_stride=st["nblk"] if clipped else 0, seg_off=st["seg"], blk2seg=st["b2s"], blk2chunk=st["b2c"],
+                         n_tensors=len(ps), n_blocks=st["nblk"], active=None if all(act_host) else st["active"], lr=float(group["lr"]),
+                         beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]), weight_decay=float(group["weight_decay"]),
+                         step=st["step"] + 1, gate=gate, clip=st["clip"] if clipped else None, max_norm=self.max_grad_norm or 0.0,
+                         ema=st["ema"], ema_decay=self.ema_decay or 0.0, ema_warmup=int(self.ema_warmup), ema_n=st["ema_n"])
+            L.check(lb.crd_diffgradnorm_step(C.byref(d), L.stream()), "crd_diffgradnorm_step")
+            if clipped:
+                self.grad_norm = st["clip"][0].clone()        # (enqueued: no sync)
+            if gate is not None:
+                skipped = bool(int(gate[4]))            # the one read of the step
+                gate[:2].zero_()                         # the next window starts without a verdict
+                self.found_inf = skipped
+                if skipped:
+                    self.skipped_steps += 1
+                    continue
+                if st["ema"] is not None:
+                    st["ema_n"] += 1                 # (the device counted it itself: gate[2])
+            self._count_step(st, ps, act_host)
             self._mark_changed(ps)
         return loss
 
@@ -222,11 +248,6 @@ class diffGradNorm(Optimizer):
             if ow is not None and ow() is not None:
                 ow().mark_params_changed()
 
-    def _ema_args(self, st, gated):
-        """The _ema entry points' tail: the buffer, decay, warm-up and -- ungated -- the number of this update (st["ema_n"] counts it
-        already), gated the base of the device's count (the gate and the EMA of a group start together: 0)."""
-        return (st["ema"].data_ptr(), self.ema_decay, 1 if self.ema_warmup else 0, 0 if gated else st["ema_n"])
-
     def ema_state(self):
         """parameter -> its EMA (a view of the group's EMA buffer, the parameter's shape)."""
         if self.ema_decay is None:
@@ -234,57 +255,6 @@ class diffGradNorm(Optimizer):
         if self._groups is None:
             self._groups = [self._build(g) for g in self.param_groups]
         return {p: st["ema"][o:o + p.numel()].view(p.shape) for st in self._groups for p, o in zip(st["ps"], st["offs"])}
-
-    def _gated_step(self, lb, group, st, ps, pbase, gptr, act_host):
-        """The gated and / or clipped launches of one group (norm pass, then the commit); -> True if the step was skipped."""
-        gate = self._gate(st, ps) if self.skip_nonfinite else None
-        active = None if all(act_host) else st["active"].data_ptr()
-        beta1, beta2 = group["betas"]
-        hyper = (float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]), st["step"] + 1, None)
-        if self.max_grad_norm is None:
-            L.check(lb.crd_diffgradnorm_norm_gated(pbase, gptr, st["nsq"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(),
-                                                   st["b2c"].data_ptr(), st["nblk"], active, float(group["weight_decay"]), None,
-                                                   gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
-            args = (pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(), st["egn"].data_ptr(), st["nsq"].data_ptr(),
-                    st["fac"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"], active,
-                    *hyper, gate.data_ptr())
-            if st["ema"] is not None:
-                L.check(lb.crd_diffgradnorm_commit_gated_ema(*args, *self._ema_args(st, True), L.stream()),
-                        "crd_diffgradnorm_commit_gated_ema")
-            else:
-                L.check(lb.crd_diffgradnorm_commit_gated(*args, L.stream()), "crd_diffgradnorm_commit_gated")
-        else:
-            if st["parts"] is None:
-                st["parts"] = torch.zeros(4 * st["nblk"], dtype=torch.float32, device=ps[0].device)
-                st["clip"] = torch.zeros(2, dtype=torch.float32, device=ps[0].device)
-            gp = None if gate is None else gate.data_ptr()
-            L.check(lb.crd_diffgradnorm_norm_clip(pbase, gptr, st["parts"].data_ptr(), st["nblk"], st["seg"].data_ptr(),
-                                                  st["b2s"].data_ptr(), st["b2c"].data_ptr(), st["nblk"], active,
-                                                  float(group["weight_decay"]), None, gp, L.stream()), "crd_diffgradnorm_norm_clip")
-            args = (pbase, gptr, st["m"].data_ptr(), st["v"].data_ptr(), st["pg"].data_ptr(), st["egn"].data_ptr(), st["parts"].data_ptr(),
-                    st["nblk"], st["fac"].data_ptr(), st["seg"].data_ptr(), st["b2s"].data_ptr(), st["b2c"].data_ptr(), len(ps), st["nblk"],
-                    active, *hyper[:6], None, self.max_grad_norm, st["clip"].data_ptr(), gp)
-            if st["ema"] is not None:
-                if gate is None:
-                    st["ema_n"] += 1
-                L.check(lb.crd_diffgradnorm_commit_clip_ema(*args, *self._ema_args(st, gate is not None), L.stream()),
-                        "crd_diffgradnorm_commit_clip_ema")
-            else:
-                L.check(lb.crd_diffgradnorm_commit_clip(*args, L.stream()), "crd_diffgradnorm_commit_clip")
-            self.grad_norm = st["clip"][0].clone()        # (enqueued: no sync)
-        if gate is None:
-            self._count_step(st, ps, act_host)
-            return False
-        skipped = bool(int(gate[4]))            # the one read of the step
-        gate[:2].zero_()                         # the next window starts without a verdict
-        self.found_inf = skipped
-        if skipped:
-            self.skipped_steps += 1
-            return True
-        self._count_step(st, ps, act_host)
-        if st["ema"] is not None:
-            st["ema_n"] += 1                 # (the device counted it itself: gate[2])
-        return False
 
     def _count_step(self, st, ps, act_host):
         st["step"] += 1

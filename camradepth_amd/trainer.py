@@ -13,6 +13,7 @@ transfer overlaps the remaining backward.  The masked-mean denominators are made
 (one 16-float all-reduce), which reproduces the reference's loss over the gathered batch exactly.
 """
 import contextlib
+import ctypes as C
 import math
 import os
 
@@ -21,7 +22,7 @@ import torch.distributed as dist
 
 from . import lib as L
 from . import trace
-from .optim import _CHUNK, check_ema_decay, check_max_grad_norm, ema_weight
+from .optim import _CHUNK, check_ema_decay, check_max_grad_norm, dgn_desc, ema_weight
 
 LOSS_W = (1.0, 1.0, 1.0, 0.2, 0.2)   # runner.py:213
 
@@ -143,12 +144,12 @@ class TrainState:
         self.nt, self.nblk = nt, len(b2s)
         self.nsq = torch.zeros(self.nblk, device=dev)        # per-workgroup parts of ||g||^2 (summed in a fixed order)
         # hyper-parameters of the next optimizer step: [0..4] read by every optimizer kernel, [8..14] by the gated one only (fp64 lr,
-        # beta1, beta2 and the host's step number: include/camradepth_hip.h, crd_diffgradnorm_commit_gated)
+        # beta1, beta2 and the host's step number: include/camradepth_hip.h, crd_dgn_desc)
         self.hp = torch.zeros(16, device=dev)
         self.hp_ring = [torch.zeros(16).pin_memory() for _ in range(64)]
         self.gate = None             # skip_nonfinite: int32[8] verdict words and step counters on the device (TrainStep._gate)
         # max_grad_norm: the norm pass's 4 rows of per-workgroup parts and [total, coef] of the last closed window
-        # (include/camradepth_hip.h, crd_diffgradnorm_norm_clip / crd_diffgradnorm_commit_clip)
+        # (include/camradepth_hip.h, crd_dgn_desc: parts, clip)
         self.max_grad_norm = max_grad_norm
         self.parts = torch.zeros(4 * self.nblk, device=dev) if max_grad_norm is not None else None
         self.clip = torch.zeros(2, device=dev) if max_grad_norm is not None else None
@@ -347,10 +348,6 @@ class TrainStep:
             self._swap_ema()
             self._ema_swapped = False
 
-    def _ema_args(self, gated):
-        """The _ema entry points' tail arguments.  Under hp (always, here) the kernels read w_n / decay / base / warm-up from it."""
-        return (self.ema.data_ptr(), self.ema_decay, 1 if self.ema_warmup else 0, self.ema_base if gated else 0)
-
     def optimizer_state(self):
         """diffGradNorm's state in the reference's per-parameter form (diffGradNorm.py:63-71), with `step` = committed steps: what
         the reference's optimizer.state_dict() holds (runner.py:369).  Tensors are views of the device buffers."""
@@ -428,18 +425,25 @@ class TrainStep:
                                               self.H * self.W, self.acc.data_ptr() + 96, None, LOSS_W[3] * scale,
                                               p.seg_grad_in.data_ptr(), st()), "crd_ce_focal_bwd")
 
-    def _optimizer(self, key=None):
-        """key: only the tensors of that gradient bucket (block-table slice + `active` mask)."""
+    def _dgn(self, key=None, gated=False, clipped=False):
+        """crd_dgn_desc of one optimizer call (by reference, for the library).  key: only the tensors of that gradient bucket (its slice
+        of the norm parts and block tables + its `active` mask; the per-tensor buffers stay whole).  gated / clipped: with the verdict
+        words / the clipping buffers.  Always under hp: the scalar hyper-parameters stay 0, the kernels read w_n / decay / base /
+        warm-up of the EMA from it."""
         m = self.model
         b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
-        args = (m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.pg.data_ptr(), self.egn.data_ptr(),
-                self.nsq.data_ptr() + 4 * b0, self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0,
-                self.b2c.data_ptr() + 4 * b0, self.nt, nb, None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1,
-                self.hp.data_ptr())
-        if getattr(self, "ema", None) is not None:         # the update kernel's EMA instantiation: the same launches
-            L.check(self.lib.crd_diffgradnorm_step_ema(*args, *self._ema_args(False), L.stream()), "crd_diffgradnorm_step_ema")
-        else:
-            L.check(self.lib.crd_diffgradnorm_step(*args, L.stream()), "crd_diffgradnorm_step")
+        ema = getattr(self, "ema", None)
+        return C.byref(dgn_desc(
+            p=m.flat, g=m.flat_grad, exp_avg=self.m, exp_avg_sq=self.v, prev_grad=self.pg, exp_grad_norm=self.egn, factor=self.fac,
+            parts=(self.parts if clipped else self.nsq).data_ptr() + 4 * b0, parts_stride=self.nblk if clipped else 0, seg_off=self.seg,
+            blk2seg=self.b2s.data_ptr() + 4 * b0, blk2chunk=self.b2c.data_ptr() + 4 * b0, n_tensors=self.nt, n_blocks=nb, active=mask,
+            hp_dev=self.hp, gate=self.gate if gated else None, clip=self.clip if clipped else None,
+            max_norm=self.max_grad_norm if clipped else 0.0, ema=ema, ema_decay=self.ema_decay if ema is not None else 0.0,
+            ema_warmup=int(self.ema_warmup) if ema is not None else 0, ema_base=self.ema_base if ema is not None and gated else 0))
+
+    def _optimizer(self, key=None):
+        """key: only the tensors of that gradient bucket (block-table slice + `active` mask)."""
+        L.check(self.lib.crd_diffgradnorm_step(self._dgn(key), L.stream()), "crd_diffgradnorm_step")
         # the bucket's new weights in the kernels' bf16 layouts, right behind its update (late stream: under the encoder's
         # backward) instead of one 169-us launch at the head of the next forward
         lo, hi = (None, None) if key is None else self.sync.ranges[key]
@@ -450,48 +454,21 @@ class TrainStep:
         L.check(self.lib.crd_nonfinite_capture(self.gate.data_ptr() + 4 if window else None, L.stream()), "crd_nonfinite_capture")
 
     def _norm_gated(self, key=None):
-        m = self.model
-        b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
-        L.check(self.lib.crd_diffgradnorm_norm_gated(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.nsq.data_ptr() + 4 * b0,
-                                                     self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0, self.b2c.data_ptr() + 4 * b0, nb,
-                                                     None if mask is None else mask.data_ptr(), 0.0, self.hp.data_ptr(),
-                                                     self.gate.data_ptr(), L.stream()), "crd_diffgradnorm_norm_gated")
+        L.check(self.lib.crd_diffgradnorm_norm(self._dgn(key, gated=True), L.stream()), "crd_diffgradnorm_norm")
 
     def _commit_gated(self):
         """Every tensor's scalar and update, or none of them, then the re-pack of all weights (of unchanged ones after a skip: the
         packed forms are a function of the fp32 parameters, so re-packing them writes the same bits)."""
-        m, mask = self.model, self.trainable_mask
-        args = (m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.pg.data_ptr(), self.egn.data_ptr(),
-                self.nsq.data_ptr(), self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(), self.nt, self.nblk,
-                None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1, self.hp.data_ptr(), self.gate.data_ptr())
-        if getattr(self, "ema", None) is not None:
-            L.check(self.lib.crd_diffgradnorm_commit_gated_ema(*args, *self._ema_args(True), L.stream()), "crd_diffgradnorm_commit_gated_ema")
-        else:
-            L.check(self.lib.crd_diffgradnorm_commit_gated(*args, L.stream()), "crd_diffgradnorm_commit_gated")
+        L.check(self.lib.crd_diffgradnorm_commit(self._dgn(gated=True), L.stream()), "crd_diffgradnorm_commit")
         self.plan.pack()
 
     # max_grad_norm pieces: the norm pass that also writes the parts of the global norm (per bucket or all; gated with
     # skip_nonfinite), and the commit: total + coefficient, every tensor's scalar and update, the re-pack
     def _norm_clip(self, key=None):
-        m = self.model
-        b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
-        L.check(self.lib.crd_diffgradnorm_norm_clip(m.flat.data_ptr(), m.flat_grad.data_ptr(), self.parts.data_ptr() + 4 * b0, self.nblk,
-                                                    self.seg.data_ptr(), self.b2s.data_ptr() + 4 * b0, self.b2c.data_ptr() + 4 * b0, nb,
-                                                    None if mask is None else mask.data_ptr(), 0.0, self.hp.data_ptr(),
-                                                    self.gate.data_ptr() if self.skip_nonfinite else None, L.stream()),
-                "crd_diffgradnorm_norm_clip")
+        L.check(self.lib.crd_diffgradnorm_norm(self._dgn(key, gated=self.skip_nonfinite, clipped=True), L.stream()), "crd_diffgradnorm_norm")
 
     def _commit_clip(self):
-        m, mask = self.model, self.trainable_mask
-        args = (m.flat.data_ptr(), m.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.pg.data_ptr(), self.egn.data_ptr(),
-                self.parts.data_ptr(), self.nblk, self.fac.data_ptr(), self.seg.data_ptr(), self.b2s.data_ptr(), self.b2c.data_ptr(),
-                self.nt, self.nblk, None if mask is None else mask.data_ptr(), 0.0, 0.0, 0.0, 0.0, 0.0, 1, self.hp.data_ptr(),
-                self.max_grad_norm, self.clip.data_ptr(), self.gate.data_ptr() if self.skip_nonfinite else None)
-        if getattr(self, "ema", None) is not None:
-            L.check(self.lib.crd_diffgradnorm_commit_clip_ema(*args, *self._ema_args(self.skip_nonfinite), L.stream()),
-                    "crd_diffgradnorm_commit_clip_ema")
-        else:
-            L.check(self.lib.crd_diffgradnorm_commit_clip(*args, L.stream()), "crd_diffgradnorm_commit_clip")
+        L.check(self.lib.crd_diffgradnorm_commit(self._dgn(gated=self.skip_nonfinite, clipped=True), L.stream()), "crd_diffgradnorm_commit")
         self.plan.pack()
 
     def _deferred(self):
@@ -750,7 +727,7 @@ class TrainStep:
             hp_host[4] = lr * math.sqrt(bc2) / (bc1 + 1e-8)
             if ema:
                 # [5] w_n of this update as the host counts it (the ungated kernels); [6], [7], [15]: decay, base and warm-up, from
-                # which the gated commit forms w_n for the device's own count (include/camradepth_hip.h, crd_diffgradnorm_*_ema)
+                # which the gated commit forms w_n for the device's own count (include/camradepth_hip.h, crd_dgn_desc)
                 if not getattr(self, "skip_nonfinite", False):
                     self.ema_n += 1
                 hp_host[5], hp_host[6] = ema_weight(self.ema_decay, self.ema_warmup, max(self.ema_n, 1))[1], self.ema_decay

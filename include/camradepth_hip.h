@@ -64,7 +64,7 @@ int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
 int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 9        /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 10       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -662,87 +662,81 @@ int crd_smoothness_bwd(const float* pred, const float* image, int32_t B, int32_t
                        const float* gout, float gmul, float* dpred, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * diffGradNorm.step (src/models/diffGradNorm.py:41-113) over flat fp32 buffers.
- * Tensor t occupies [seg_off[2t], seg_off[2t+1]) of every flat buffer (int64 pairs; gaps allowed).  Workgroup w processes chunk
- * blk2chunk[w] (4096 elements) of tensor blk2seg[w]; the workgroups of a tensor are consecutive and in chunk order.
- * exp_grad_norm / factor are float[n_tensors]; norm_sq is scratch, float[n_blocks]: workgroup w stores its part of
- * ||g||^2 in norm_sq[w] and one wave per tensor adds its workgroups' parts in a fixed order (reproducible; the e > n
- * branch of diffGradNorm.py:84 turns rounding noise into a discrete jump).  active[t]=0 skips tensor t
- * (`p.grad is None`, :54-55).  `step` is the 1-based step count used for the bias corrections.
- * hp_dev (optional, device float[5] = beta1, beta2, eps, weight_decay, lr*sqrt(1-beta2^t)/(1-beta1^t+1e-8))
- * overrides the scalar arguments so that a captured HIP graph can follow a per-iteration schedule.
- * ------------------------------------------------------------------------------------------- */
-int crd_diffgradnorm_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                          float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
-                          const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                          const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                          int32_t step, const float* hp_dev, crd_stream_t stream);
-/* The same optimizer step split in two and GATED (skip_nonfinite, GradScaler.step semantics): nothing is written when the window saw a
- * non-finite gradient.  gate: device int32[8], zeroed by the caller except for the counters: [0] a gradient element was NaN / inf (set
- * by crd_diffgradnorm_norm_gated), [1] a crd_sum_t partial was dropped during the window's backward (crd_nonfinite_capture), [2]
- * committed steps, [3] skipped steps, [4] the verdict of the last window (1 = skipped), [5] scratch (the step size in use).
- * norm_gated: k_dgn_norm's pass over the blocks given (one bucket may be passed at a time: norm_sq / blk2seg / blk2chunk then point at
- * that bucket's slice) plus the finiteness test.  commit_gated: the per-tensor scalars and the update over all blocks, or none.
- * Bias corrections: `step` / lr / beta1 / beta2 when hp_dev is NULL (the host knows every verdict); with hp_dev, hp_dev[4] as long as
- * the device count of this step equals the host's step number (int32 at hp_dev[14]), otherwise computed on the device in fp64 from
- * the fp64 lr, beta1, beta2 at hp_dev[8..13].  hp_dev is then float[16]. */
-int crd_diffgradnorm_norm_gated(const float* p, const float* g, float* norm_sq, const int64_t* seg_off, const int32_t* blk2seg,
-                                const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active, float weight_decay,
-                                const float* hp_dev, int32_t* gate, crd_stream_t stream);
-int crd_diffgradnorm_commit_gated(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                  float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
-                                  const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                  const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                  int32_t step, const float* hp_dev, int32_t* gate, crd_stream_t stream);
-/* The optimizer step behind torch.nn.utils.clip_grad_norm_(params, max_norm) (max_grad_norm): every gradient is scaled by
- * coef = min(1, max_norm / (total + 1e-6)), total = the 2-norm over all blocks given, before the weight decay is added; the norm,
- * exp_avg, exp_avg_sq and previous_grad all see the scaled gradient.  The gradient buffer itself is not written.
- * parts: device float[4 * parts_stride], four rows of per-workgroup parts: [0] sum (g + wd p)^2 (what norm_sq holds above), [1] sum
- * g^2, [2] sum g p and [3] sum p^2 (rows 2 and 3: with weight decay only).  norm_clip: k_dgn_norm's pass over the blocks given, which
- * also writes rows 1-3 (one bucket may be passed at a time, as for norm_gated: `parts` then points at that bucket's first block
- * and parts_stride stays the full count); gate (optional): the finiteness test of norm_gated.  commit_clip: ONE workgroup adds row 1
- * over all n_blocks in a fixed order in fp64 and writes clip[0] = total, clip[1] = coef (device float[2]; torch's fp32 coefficient,
- * a NaN total gives NaN), then the per-tensor scalars (from row 0 when coef == 1, else from rows 1-3) and the update.  coef == 1
- * gives the bits of crd_diffgradnorm_step / crd_diffgradnorm_commit_gated.  gate (optional): crd_diffgradnorm_commit_gated's
- * semantics (gate[0] set by norm_clip).  max_norm > 0; +inf gives coef = 1 (the total only). */
-int crd_diffgradnorm_norm_clip(const float* p, const float* g, float* parts, int64_t parts_stride, const int64_t* seg_off,
-                               const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_blocks, const uint8_t* active,
-                               float weight_decay, const float* hp_dev, int32_t* gate, crd_stream_t stream);
-int crd_diffgradnorm_commit_clip(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                 float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
-                                 const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
-                                 int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
-                                 int32_t* gate, crd_stream_t stream);
-/* ema_decay: the three commit paths above with an exponential moving average of the parameters updated in the same pass.  ema:
- * device fp32 buffer with the layout of p.  For every element the update kernel writes (active tensors of a committed step only),
- * in fp32:   d_n = ema_warmup ? fminf(ema_decay, (float)(1 + n) / (float)(10 + n)) : ema_decay;   w_n = 1.0f - d_n;
+ * diffGradNorm.step (src/models/diffGradNorm.py:41-113) over flat fp32 buffers: one descriptor, three entry points.
+ * Three independent switches, each a nullable pointer of the descriptor: gate (skip_nonfinite), clip (max_grad_norm), ema
+ * (ema_decay).  Which kernel instantiations run follows from gate != NULL, clip != NULL, ema != NULL and nothing else.
+ *
+ * Layout.  Tensor t occupies [seg_off[2t], seg_off[2t+1]) of every flat buffer (int64 pairs; gaps allowed).  Workgroup w processes
+ * chunk blk2chunk[w] (4096 elements) of tensor blk2seg[w]; the workgroups of a tensor are consecutive and in chunk order.
+ * exp_grad_norm / factor are float[n_tensors].  active[t]=0 skips tensor t (`p.grad is None`, :54-55); NULL = all active.  `step` is
+ * the 1-based step count used for the bias corrections.
+ * parts is scratch: without clip float[n_blocks], ONE row: workgroup w stores its part of ||g||^2 = sum (g + wd p)^2 in parts[w] and
+ * one wave per tensor adds its workgroups' parts in a fixed order (reproducible; the e > n branch of diffGradNorm.py:84 turns
+ * rounding noise into a discrete jump).  With clip float[4 * parts_stride], four rows of per-workgroup parts: [0] sum (g + wd p)^2
+ * (the row above), [1] sum g^2, [2] sum g p and [3] sum p^2 (rows 2 and 3: with weight decay only).  parts_stride is read with clip
+ * only.
+ * hp_dev (optional, device float[5] = beta1, beta2, eps, weight_decay, lr*sqrt(1-beta2^t)/(1-beta1^t+1e-8)) overrides the scalar
+ * fields so that a captured HIP graph can follow a per-iteration schedule.  With gate or ema it is float[16], see below.
+ *
+ * crd_diffgradnorm_norm: k_dgn_norm's pass over the blocks given.  It reads only p, g, parts, parts_stride, seg_off, blk2seg,
+ * blk2chunk, n_blocks, active, weight_decay, hp_dev, gate and clip (as a flag) and demands nothing else.  One bucket may be passed
+ * at a time: parts / blk2seg / blk2chunk then point at that bucket's first block, n_blocks is the bucket's count and parts_stride
+ * stays the full count.  With gate it also tests every gradient element for finiteness; with clip it also writes rows 1-3.
+ * crd_diffgradnorm_commit: [with clip: total + coefficient,] the per-tensor scalars and the update over ALL blocks.
+ * crd_diffgradnorm_step: norm, then commit, with the same descriptor.
+ *
+ * gate (skip_nonfinite, GradScaler.step semantics): nothing is written when the window saw a non-finite gradient.  Device int32[8],
+ * zeroed by the caller except for the counters: [0] a gradient element was NaN / inf (set by crd_diffgradnorm_norm), [1] a crd_sum_t
+ * partial was dropped during the window's backward (crd_nonfinite_capture), [2] committed steps, [3] skipped steps, [4] the verdict
+ * of the last window (1 = skipped), [5] scratch (the step size in use).  The commit writes every tensor's scalar and update, or
+ * none.  Bias corrections: `step` / lr / beta1 / beta2 when hp_dev is NULL (the host knows every verdict); with hp_dev, hp_dev[4]
+ * as long as the device count of this step equals the host's step number (int32 at hp_dev[14]), otherwise computed on the device
+ * in fp64 from the fp64 lr, beta1, beta2 at hp_dev[8..13].  hp_dev is then float[16].
+ *
+ * clip (max_grad_norm): the optimizer step behind torch.nn.utils.clip_grad_norm_(params, max_norm): every gradient is scaled by
+ * coef = min(1, max_norm / (total + 1e-6)), total = the 2-norm over all blocks, before the weight decay is added; the norm,
+ * exp_avg, exp_avg_sq and previous_grad all see the scaled gradient.  The gradient buffer itself is not written.  The commit: ONE
+ * workgroup adds row 1 over all n_blocks in a fixed order in fp64 and writes clip[0] = total, clip[1] = coef (device float[2];
+ * torch's fp32 coefficient, a NaN total gives NaN), then the per-tensor scalars (from row 0 when coef == 1, else from rows 1-3) and
+ * the update.  coef == 1 gives the bits of the step without clip.  Row 1 is added over the commit's n_blocks, so commit and step
+ * require parts_stride == n_blocks with clip: a commit over one bucket's slice would clip with a partial norm.  max_norm > 0; +inf
+ * gives coef = 1 (the total only).  With gate: the gate's semantics above (gate[0] set by the norm pass).
+ *
+ * ema (ema_decay): an exponential moving average of the parameters updated in the same pass; a device fp32 buffer with the layout
+ * of p.  For every element the update kernel writes (active tensors of a committed step only), in fp32:
+ *            d_n = ema_warmup ? fminf(ema_decay, (float)(1 + n) / (float)(10 + n)) : ema_decay;   w_n = 1.0f - d_n;
  *            ema = fmaf(w_n, p_new - ema, ema)          (p_new: the value stored to p; 0 <= ema_decay < 1)
  * n = 1, 2, ... counts the committed steps since the EMA was created or restored.  Without a gate the host knows it: ema_n = n, or
  * with hp_dev the host leaves w_n itself in hp_dev[5] (ema_n is then ignored), so a captured graph follows n without re-capture.
  * With a gate only the device knows which steps were committed: n = gate[2] (after this step's verdict) - ema_base, w_n is formed
  * on the device by the expression above; with hp_dev, ema_decay / ema_base / ema_warmup are read from hp_dev[6], the int32 at
- * hp_dev[7] and the int32 at hp_dev[15].  crd_diffgradnorm_commit_clip_ema: ema_n is n without a gate, ema_base with one.
- * Everything else -- p, the optimizer state, the status codes -- is what the entry point without _ema does, bit for bit. */
-int crd_diffgradnorm_step_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                              float* exp_grad_norm, float* norm_sq, float* factor, const int64_t* seg_off,
-                              const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                              const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                              int32_t step, const float* hp_dev, float* ema, float ema_decay, int32_t ema_warmup, int32_t ema_n,
-                              crd_stream_t stream);
-int crd_diffgradnorm_commit_gated_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                      float* exp_grad_norm, const float* norm_sq, float* factor, const int64_t* seg_off,
-                                      const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors, int32_t n_blocks,
-                                      const uint8_t* active, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                      int32_t step, const float* hp_dev, int32_t* gate, float* ema, float ema_decay,
-                                      int32_t ema_warmup, int32_t ema_base, crd_stream_t stream);
-int crd_diffgradnorm_commit_clip_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* prev_grad,
-                                     float* exp_grad_norm, const float* parts, int64_t parts_stride, float* factor,
-                                     const int64_t* seg_off, const int32_t* blk2seg, const int32_t* blk2chunk, int32_t n_tensors,
-                                     int32_t n_blocks, const uint8_t* active, float lr, float beta1, float beta2, float eps,
-                                     float weight_decay, int32_t step, const float* hp_dev, float max_norm, float* clip,
-                                     int32_t* gate, float* ema, float ema_decay, int32_t ema_warmup, int32_t ema_n,
-                                     crd_stream_t stream);
+ * hp_dev[7] and the int32 at hp_dev[15].  ema_n is read without a gate only, ema_base with one only.
+ * Everything else -- p, the optimizer state, the status codes -- is what the call with ema = NULL does, bit for bit.
+ *
+ * CRD_E_INVALID before any launch: a NULL descriptor, buffer or table, n_blocks <= 0; commit / step: n_tensors <= 0, step < 1; clip:
+ * parts_stride < n_blocks, and on commit / step max_norm not > 0 (NaN included) or parts_stride != n_blocks; ema on commit / step:
+ * ema_decay outside [0, 1), ema_base < 0 with a gate, ema_n < 1 without one (ema_n < 0 with hp_dev).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct crd_dgn_desc {
+  float* p; const float* g; float* exp_avg; float* exp_avg_sq; float* prev_grad; float* exp_grad_norm; float* factor;
+  float* parts;                                       /* per-workgroup norm parts: 1 row, with clip 4 rows parts_stride apart */
+  const int64_t* seg_off; const int32_t* blk2seg; const int32_t* blk2chunk;
+  const uint8_t* active;                              /* nullable */
+  const float* hp_dev;                                /* nullable: overrides the scalars below */
+  int32_t* gate;                                      /* NULL = ungated */
+  float* clip;                                        /* NULL = no clipping; [total, coef] */
+  float* ema;                                         /* NULL = no EMA */
+  int64_t parts_stride;
+  int32_t n_tensors, n_blocks;
+  float lr, beta1, beta2, eps, weight_decay;
+  int32_t step;
+  float max_norm;
+  float ema_decay;
+  int32_t ema_warmup, ema_n, ema_base;
+} crd_dgn_desc;
+int crd_diffgradnorm_norm(const crd_dgn_desc* d, crd_stream_t stream);
+int crd_diffgradnorm_commit(const crd_dgn_desc* d, crd_stream_t stream);
+int crd_diffgradnorm_step(const crd_dgn_desc* d, crd_stream_t stream);
 /* a[i] <-> b[i] for i < n, in place (no temporary): two fp32 buffers that do not overlap, any 4-byte alignment (16-byte loads and
  * stores where both buffers allow them, single elements at the ends); n = 0 does nothing.  Exchanges the parameters with their EMA. */
 int crd_swap_f32(float* a, float* b, int64_t n, crd_stream_t stream);

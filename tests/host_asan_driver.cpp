@@ -33,6 +33,9 @@ int main() {
   // argument checks return before any launch
   printf("null conv: %d (%s)\n", crd_conv_igemm(nullptr, nullptr), crd_last_error());
   printf("null wgrad: %d (%s)\n", crd_conv_wgrad(nullptr, nullptr), crd_last_error());
+  printf("null dgn: %d (%s)\n", crd_diffgradnorm_step(nullptr, nullptr), crd_last_error());
+  crd_dgn_desc z; memset(&z, 0, sizeof z);
+  printf("zeroed dgn: %d (%s)\n", crd_diffgradnorm_step(&z, nullptr), crd_last_error());
   printf("version %d arch %s\n", crd_version(), crd_arch());
   return 0;
 }

@@ -68,7 +68,12 @@ def test_struct_layouts_match_header(built, tmp_path):
               "crd_wgrad_desc": (built.WgradDesc, ["x", "dy", "Cout", "dw", "dbias", "dw_partials", "dw_partial_capacity", "wg_budget"]),
               "crd_pack_entry": (built.PackEntry, ["src", "cmap", "Cout", "dst_f32", "dgrad_ld", "dgrad_rows"]),
               "crd_unpack_entry": (built.UnpackEntry, ["src", "cmap", "Cin_pad", "replicas", "replica_stride"]),
-              "crd_wgrad_group_info": (built.WgradGroupInfo, ["n_problems", "n_items", "item_offset", "bytes"])}
+              "crd_wgrad_group_info": (built.WgradGroupInfo, ["n_problems", "n_items", "item_offset", "bytes"]),
+              "crd_dgn_desc": (built.DgnDesc, ["p", "g", "exp_avg", "exp_avg_sq", "prev_grad", "exp_grad_norm", "factor", "parts", "seg_off",
+                                               "blk2seg", "blk2chunk", "active", "hp_dev", "gate", "clip", "ema", "parts_stride", "n_tensors",
+                                               "n_blocks", "lr", "beta1", "beta2", "eps", "weight_decay", "step", "max_norm", "ema_decay",
+                                               "ema_warmup", "ema_n", "ema_base"])}
+    assert fields["crd_dgn_desc"][1] == [n for n, _ in built.DgnDesc._fields_]           # every field of the optimizer's descriptor
     src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{REPO}/include/camradepth_hip.h"', "int main(void){"]
     for cname, (_, fl) in fields.items():
         src.append(f'printf("{cname} %zu", sizeof({cname}));')
@@ -96,6 +101,44 @@ def test_invalid_arguments_are_reported_without_a_gpu(built):
     assert rc == -1 and b"null" in L.crd_last_error()
     with pytest.raises(built.CrdError):
         built.check(rc, "crd_conv_igemm")
+
+
+def test_diffgradnorm_descriptor_is_validated_without_a_gpu(built):
+    """crd_dgn_desc: one validation for crd_diffgradnorm_norm / _commit / _step, which refuses before any launch."""
+    L = built.load()
+    buf = ctypes.create_string_buffer(64)          # any non-NULL host address: a refused call launches nothing and reads none of it
+    a = ctypes.addressof(buf)
+
+    def desc(**kw):
+        d = built.DgnDesc(**dict(dict(n_tensors=1, n_blocks=2, step=1, beta1=0.9, beta2=0.999, lr=1e-3, eps=1e-8), **kw))
+        for n, t in built.DgnDesc._fields_:
+            if t is ctypes.c_void_p and n not in ("active", "hp_dev", "gate", "clip", "ema") and n not in kw:
+                setattr(d, n, a)
+        return d
+
+    def refused(fn, d, word):
+        rc = fn(None if d is None else ctypes.byref(d), None)
+        msg = L.crd_last_error()
+        assert rc == -1 and fn.__name__.encode() in msg and word in msg, (fn.__name__, rc, msg)
+        with pytest.raises(built.CrdError):
+            built.check(rc, fn.__name__)
+
+    fns = (L.crd_diffgradnorm_norm, L.crd_diffgradnorm_commit, L.crd_diffgradnorm_step)
+    for fn in fns:
+        refused(fn, None, b"null")                                     # a NULL descriptor
+        refused(fn, built.DgnDesc(), b"bad argument")                  # a zeroed one
+    for fn in fns[1:]:
+        refused(fn, desc(clip=a, parts_stride=2, max_norm=0.0), b"max_norm")
+        refused(fn, desc(clip=a, parts_stride=2, max_norm=float("nan")), b"max_norm")
+        refused(fn, desc(ema=a, ema_n=1, ema_decay=1.0), b"ema_decay")
+        refused(fn, desc(ema=a, ema_n=0, ema_decay=0.5), b"ema_n")               # ungated, no hp_dev: the host numbers the update
+        refused(fn, desc(ema=a, gate=a, ema_base=-1, ema_decay=0.5), b"ema_base")
+        refused(fn, desc(clip=a, parts_stride=3, max_norm=1.0), b"parts_stride")       # a commit over a slice: partial global norm
+        refused(fn, desc(step=0), b"step")
+        refused(fn, desc(exp_avg=None), b"null")
+    refused(fns[0], desc(clip=a, parts_stride=1), b"parts_stride")     # the norm pass: rows shorter than the blocks given
+    refused(fns[0], desc(n_blocks=0), b"n_blocks")
+    refused(fns[0], desc(g=None), b"null")
 
 
 def test_module_parameter_inventory_and_flat_views():

@@ -19,7 +19,7 @@ from camradepth_amd.optim import check_ema_decay, diffGradNorm, ema_weight
 from camradepth_amd.trainer import GradSync, TrainStep
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("crd_diffgradnorm_step_ema", "crd_diffgradnorm_commit_gated_ema", "crd_diffgradnorm_commit_clip_ema", "crd_swap_f32")
+NEW = ("crd_diffgradnorm_norm", "crd_diffgradnorm_commit", "crd_diffgradnorm_step", "crd_swap_f32")
 
 
 def test_ema_decay_values_are_checked():
@@ -75,9 +75,15 @@ def test_new_symbols_are_declared_and_bound():
         assert re.search(r"\bint\s+%s\s*\(" % name, h), name
         assert name in L._SIGS and name in L.EXPORTS, name
     assert int(re.search(r"#define\s+CRD_ABI_VERSION\s+(\d+)", h).group(1)) == L.ABI_VERSION >= 9
-    # the _ema entry points take their base entry point's arguments, then (ema, decay, warmup, n | base), then the stream
-    for base in ("crd_diffgradnorm_step", "crd_diffgradnorm_commit_gated", "crd_diffgradnorm_commit_clip"):
-        assert L._SIGS[base + "_ema"] == L._SIGS[base][:-1] + "pfii" + "p"
+    # the optimizer's entry points take one descriptor and the stream; the EMA is part of the descriptor -- its buffer with the other
+    # pointers, then decay, warm-up, and the update number and the base as two separate ints -- and of no signature
+    for name in NEW[:3]:
+        assert L._SIGS[name] == "pp"
+    assert not [n for n in L._SIGS if n.startswith("crd_diffgradnorm_") and n not in NEW]
+    body = re.search(r"typedef\s+struct\s+crd_dgn_desc\s*\{(.*?)\}\s*crd_dgn_desc\s*;", h, flags=re.S).group(1)
+    declared = [n for decl in body.split(";") for n in re.findall(r"(\w+)\s*(?=,|$)", decl.strip())]     # the field names, in order
+    assert declared == [n for n, _ in L.DgnDesc._fields_]
+    assert {"ema", "ema_decay", "ema_warmup", "ema_n", "ema_base", "gate", "clip", "max_norm"} <= set(declared)
 
 
 # ---------------------------------------------------------------------------------------------- control flow (stand-ins)

@@ -657,8 +657,10 @@ def test_diffgradnorm_matches_golden_trajectory():
         lr, b1, b2 = (float(z) for z in gd["hp"][it])
         gb = torch.randn(10000, generator=g) * (0.02 if 10 <= it < 14 else 1.0)
         grads = torch.cat([torch.from_numpy(gd[f"p{j}_grads"][it]).reshape(-1) for j in range(3)] + [gb]).cuda()
-        ok(lb.crd_diffgradnorm_step(P(flat), P(grads), P(m), P(v), P(pg), P(egn), P(nsq), P(fac), P(seg), P(b2s_d), P(b2c_d),
-                                    4, len(b2s), None, lr, b1, b2, 1e-8, 0.0, it + 1, None, lib.stream()), "dgn")
+        d = lib.DgnDesc(p=P(flat), g=P(grads), exp_avg=P(m), exp_avg_sq=P(v), prev_grad=P(pg), exp_grad_norm=P(egn), parts=P(nsq),
+                        factor=P(fac), seg_off=P(seg), blk2seg=P(b2s_d), blk2chunk=P(b2c_d), n_tensors=4, n_blocks=len(b2s), active=None,
+                        lr=lr, beta1=b1, beta2=b2, eps=1e-8, weight_decay=0.0, step=it + 1, hp_dev=None)
+        ok(lb.crd_diffgradnorm_step(C.byref(d), lib.stream()), "dgn")
         ooptim.step_tensor(big_ref, gb, big_state, lr, b1, b2)
         fc = flat.cpu()
         for j in range(3):

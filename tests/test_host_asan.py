@@ -43,5 +43,6 @@ def test_host_code_is_asan_clean():
         out = r.stdout + r.stderr
         assert r.returncode == 0 and "AddressSanitizer" not in out, out[-4000:]
         assert "build rc 0" in out and "short table rc -1" in out and "splits(cap 12) = 12" in out and "null conv: -1" in out, out
+        assert "null dgn: -1" in out and "zeroed dgn: -1" in out, out
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
