@@ -99,7 +99,7 @@ class DgnDesc(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 10         # include/camradepth_hip.h: CRD_ABI_VERSION
+ABI_VERSION = 11         # include/camradepth_hip.h: CRD_ABI_VERSION
 
 
 def load():
@@ -151,7 +151,7 @@ _SIGS = {
     "crd_weight_pack": "pilp", "crd_wgrad_unpack": "pilip",
     "crd_assemble_input": "pppiiifpp", "crd_gt_pyramid": "piiifppppp",
     "crd_resize_nearest_u8": "piiiipiip", "crd_resize_labels_nearest": "piiiipiip", "crd_seg_confusion": "ppiilppp",
-    "crd_masked_l1_fwd": "pplpp", "crd_test_metrics": "ppilffpp", "crd_masked_l1_bwd": "pplppfpp", "crd_ce_fwd": "ppiilpp",
+    "crd_masked_l1_fwd": "pplpp", "crd_test_metrics": "ppilffpp", "crd_depth_eval": "ppilfffipp", "crd_masked_l1_bwd": "pplppfpp", "crd_ce_fwd": "ppiilpp",
     "crd_ce_focal_bwd": "ppiilppfpp",
     "crd_masked_dist_fwd": "pplpp", "crd_masked_dist_bwd": "pplppfipp", "crd_masked_berhu_max": "pplppp",
     "crd_masked_berhu": "pplppLppfpp", "crd_smoothness_fwd": "ppiiiipp", "crd_smoothness_bwd": "ppiiiippfpp",
@@ -167,6 +167,9 @@ EXPORTS = list(_SIGS)
 # crd_sum_t (include/camradepth_hip.h): 64-bit fixed-point accumulators, value = integer * 2^-FRAC_BITS
 STAT_FRAC_BITS, GRAD_FRAC_BITS = 20, 44
 SUM_DTYPE = torch.int64
+# crd_depth_eval: one scale per column of its [frames][bins][12] accumulator (CRD_EVAL_FRAC_BITS), at most CRD_EVAL_MAX_BINS bins
+EVAL_FRAC_BITS = (0, 32, 26, 24, 24, 36, 33, 31, 40, 0, 0, 0)
+EVAL_MAX_BINS = 64
 
 
 def stat_value(t):

@@ -14,7 +14,7 @@ import torch
 from . import lib as L
 from . import losses as HL
 from .inference import InferenceGraph
-from .metrics import DepthMetrics, SegIoU
+from .metrics import DepthEval, DepthMetrics, SegIoU
 from .optim import check_ema_decay, check_max_grad_norm
 from .trainer import TrainStep, depth_criterion_mode, one_cycle
 
@@ -156,10 +156,16 @@ class Trainer:
         return best
 
     # ------------------------------------------------------------------ test (runner.py:394-519)
-    def test(self, save=False):
+    def test(self, save=False, extended=False, caps=None):
         """Per-frame metrics of Trainer.test averaged with nanmean: RMSE / MAE / REL within max_distances[0], the second set
-        with ground truth below max_distances[1] dropped as well (runner.py:489-491), IoU (supervised seg), mean forward time."""
+        with ground truth below max_distances[1] dropped as well (runner.py:489-491), IoU (supervised seg), mean forward time.
+
+        extended=True adds the standard depth-evaluation suite (camradepth_amd.metrics.DepthEval, one more kernel per batch):
+        "extended" maps each cap in `caps` (metres of true distance; default max_distances) to DepthEval.result(cap) -- delta
+        accuracies, AbsRel, SqRel, RMSElog, SILog, iRMSE / iMAE, MAE, RMSE over the ground truth WITHIN the cap -- and "by_range"
+        is DepthEval.by_range().  The other keys, and with extended=False the whole result and the work done, are unchanged."""
         self.model.eval()
+        ev = DepthEval(self.max_depth) if extended else None
         m100, m50 = DepthMetrics(self.max_depth, self.max_distances[0]), DepthMetrics(self.max_depth, self.max_distances[0])
         iou = SegIoU(self.num_classes) if self.cfg.supervised_seg else None
         times = []
@@ -176,6 +182,8 @@ class Trainer:
                 m100.update(fd, gt)
                 gt50 = torch.where(gt * self.max_depth < self.max_distances[1], torch.zeros_like(gt), gt)
                 m50.update(fd, gt50)
+                if ev is not None:
+                    ev.update(fd, gt)
                 if iou is not None and out["seg"]["final_seg"] is not None and "seg" in b:
                     iou.update(out["seg"]["final_seg"], b["seg"].cuda())
         self.model.train()
@@ -183,4 +191,7 @@ class Trainer:
         res = {"time": _nanmean(times), "max_depth_%g" % self.max_distances[0]: r100, "max_depth_%g" % self.max_distances[1]: r50}
         if iou is not None:
             res["IoU"] = iou.result()
+        if ev is not None:
+            res["extended"] = {cap: ev.result(cap) for cap in (self.max_distances if caps is None else tuple(caps))}
+            res["by_range"] = ev.by_range()
         return res

@@ -64,7 +64,7 @@ int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
 int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 10       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 11       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -614,6 +614,50 @@ int crd_test_metrics(const float* pred, const float* gt, int32_t frames, int64_t
  * in out_of_range[f] (torchmetrics raises ValueError on them, which the reference catches: that frame's IoU is NaN). */
 int crd_seg_confusion(const float* logits, const int64_t* labels, int32_t frames, int32_t C, int64_t HW, int64_t* confmat,
                       int64_t* out_of_range, crd_stream_t stream);
+/* The standard depth-evaluation sums (threshold accuracies, AbsRel, SqRel, RMSE(log), SILog, iRMSE / iMAE, ...) of `frames` fp32
+ * maps of n pixels each, binned by TRUE distance so that one pass serves every distance cap; no host sync.
+ * pred, gt: normalised INVERTED depth (gt = (max_depth - d) / max_depth for a lidar hit, 0 = no hit).  Per pixel, in fp32, every
+ * statement rounded on its own (no contraction into fused multiply-adds):
+ *   dg    = max_depth * (1.0f - gt)                                        the true distance in metres
+ *   valid = gt > 0 and dg >= min_depth
+ *   dp    = min(max(max_depth * (1.0f - clamp(pred, 0, 1)), min_depth), max_depth)      (a NaN pred stays NaN through the clamps)
+ *   bin   = min(n_bins - 1, (int)floorf(dg / bin_width)),   n_bins = ceil(max_depth / bin_width)
+ *   e = dp - dg,  r = logf(dp) - logf(dg),  q = 1/dp - 1/dg,  m = max(dp/dg, dg/dp)
+ * acc[f][bin][c] += (CRD_EVAL_COLUMNS columns, caller zeroes acc)
+ *   0 count   1 |e|   2 e^2   3 |e|/dg   4 e^2/dg   5 r   6 r^2   7 |q|   8 q^2   9 #(m < 1.25)   10 #(m < 1.25^2)   11 #(m < 1.25^3)
+ * For a cap c (a multiple of bin_width) add the bins below c / bin_width; with n = column 0 and s1..s11 the others:
+ *   MAE = s1/n, RMSE = sqrt(s2/n), AbsRel = s3/n, SqRel = s4/n, RMSElog = sqrt(s6/n), SILog = 100 sqrt(max(0, s6/n - (s5/n)^2)),
+ *   iMAE = 1000 s7/n and iRMSE = 1000 sqrt(s8/n) (1/km), delta_k = s(8+k)/n.
+ * acc is crd_sum_t with ONE FIXED-POINT SCALE PER COLUMN: value = acc * 2^-CRD_EVAL_FRAC_BITS[c] (the 2^-20 grid of
+ * CRD_STAT_FRAC_BITS is too coarse for a per-pixel |q| of 1e-3).  Every per-pixel term is rounded once to its column's grid and
+ * added as an integer (a table per workgroup in LDS, then one 64-bit integer add per non-zero entry): the sums do not depend on
+ * the order of arrival, and two calls give identical bits.  A term that is not finite or whose scaled magnitude reaches 2^62
+ * adds nothing and raises the sticky flag (crd_nonfinite_status).  Ranges per (frame, bin) -- |sum| < 2^(63 - bits) -- and the
+ * largest per-pixel term at max_depth = 100, min_depth = 1e-3 (dg, dp in [1e-3, 100]):
+ *   column  bits  grid      sum below   largest term            928 x 1600 all-valid pixels (1.48e6) in ONE bin
+ *   1       32    2.3e-10   2.1e9       100                     1.5e8   fits
+ *   2       26    1.5e-8    1.4e11      1e4                     1.5e10  fits
+ *   3       24    6.0e-8    5.5e11      1e5                     1.5e11  fits
+ *   4       24    6.0e-8    5.5e11      1e7                     1.5e13  DOES NOT fit in the worst case: the sum of e^2/dg over a
+ *                                                               (frame, bin) must stay below 5.5e11 m, a mean of 3.7e5 m over such a
+ *                                                               frame -- held whenever no ground truth is closer than 2.7 cm
+ *   5       36    1.5e-11   1.3e8       11.6                    1.7e7   fits
+ *   6       33    1.2e-10   1.1e9       133                     2.0e8   fits
+ *   7       31    4.7e-10   4.3e9       1e3                     1.5e9   fits
+ *   8       40    9.1e-13   8.4e6       1e6                     1.5e12  DOES NOT fit in the worst case: the sum of q^2 over a
+ *                                                               (frame, bin) must stay below 8.4e6 m^-2, a mean of 5.6 m^-2 over
+ *                                                               such a frame (an rms inverse-depth error of 2.4 per metre)
+ *   0, 9-11 0     1         9.2e18      1
+ * A sum that leaves its range wraps around silently (the per-term guard cannot see the total): columns 4 and 8 are the ones to
+ * watch with ground truth at centimetres.
+ * CRD_E_INVALID before any launch: NULL pred / gt / acc; frames <= 0; n <= 0; max_depth, min_depth or bin_width not finite and
+ * > 0; min_depth >= max_depth; n_bins != ceil(max_depth / bin_width) or > CRD_EVAL_MAX_BINS.  CRD_E_UNSUPPORTED: frames > 65535
+ * or n >= 2^35.  No read past frames * n elements; 64-bit indexing; any alignment of pred / gt and any n. */
+#define CRD_EVAL_COLUMNS 12
+#define CRD_EVAL_MAX_BINS 64
+static const int CRD_EVAL_FRAC_BITS[CRD_EVAL_COLUMNS] = {0, 32, 26, 24, 24, 36, 33, 31, 40, 0, 0, 0};
+int crd_depth_eval(const float* pred, const float* gt, int32_t frames, int64_t n, float max_depth, float min_depth, float bin_width,
+                   int32_t n_bins, crd_sum_t* acc /* [frames][n_bins][12], caller zeroes */, crd_stream_t stream);
 /* dpred = gmul * gout[0] * clamp(pred-target,-1,1) / acc[1] on target>0, else 0   (gout may be NULL = 1) */
 int crd_masked_l1_bwd(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const float* gout,
                       float gmul, float* dpred, crd_stream_t stream);
