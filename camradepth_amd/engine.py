@@ -72,9 +72,8 @@ FC2_FOLD_MINROWS = _dev_int("CRD_FC2_FOLD_MINROWS", 16384)   # (B = 16 inference
 GN_CONV_MAXROWS = _dev_int("CRD_GN_CONV_MAXROWS", 1 << 30)   # pixels x batch up to which a Block's GEMMs are fused
 # The decoder's weight gradients (2.9 ms of MFMA work nothing in the backward pass waits for) can leave the chain: the
 # single-GPU graph step replays them as a graph of their own on a second stream while the encoder's latency-bound backward
-# runs (trainer.py; CRD_NO_LATE_WGRAD keeps program order).  W3_LATE_WGS: workgroups their streaming kernels may use in
+# runs (trainer.py: every captured step).  W3_LATE_WGS: workgroups their streaming kernels may use in
 # that mode, so that the encoder's kernels still find free CUs (256: 22.1 ms, 160: 20.7, 128: 20.9, 64: 22.3).
-LATE_WGRAD = not _dev_flag("CRD_NO_LATE_WGRAD")
 W3_LATE_WGS = _dev_int("CRD_W3_LATE_WGS", 160)
 LATE = 3            # Op.stream id of those ops (0 = the main stream)
 DW_REPLICAS = tables.DW_REPLICAS

@@ -1,19 +1,15 @@
 """Training-step driver: the counterpart of `Trainer.train_one_epoch`'s inner iteration
-(reference: src/main/runner.py:179-270) for one process per GPU.
+(reference: src/main/runner.py:179-270) for one process per GPU.  TrainStep._iteration states what one iteration runs and in
+which order, for the eager and the captured step alike.
 
-One step = zero grads -> forward -> masked losses -> backward -> (gradient all-reduce) -> diffGradNorm,
-entirely as HIP kernels enqueued on one stream with static buffers, so the step is captured once
-into HIP graphs and replayed; the host only updates five hyper-parameter floats per step
-(OneCycleLR drives lr and beta1 every iteration, runner.py:151-152,270).
-
-Data parallelism replaces nn.DataParallel (runner.py:135-136): batch-sharded replicas, gradients
-SUM-all-reduced with RCCL in four buckets that become ready in backward order (decoder, stages 4+3,
-stage 2, stage 1 + patch embeds), each launched as soon as its backward segment is enqueued so the
-transfer overlaps the remaining backward.  The masked-mean denominators are made global first
-(one 16-float all-reduce), which reproduces the reference's loss over the gathered batch exactly.
+Data parallelism replaces nn.DataParallel (runner.py:135-136): batch-sharded replicas, gradients SUM-all-reduced with RCCL in four
+buckets that become ready in backward order (decoder, stages 4+3, stage 2, stage 1 + patch embeds), each launched as soon as its
+backward segment is enqueued so the transfer overlaps the remaining backward.
 """
+import collections
 import contextlib
 import ctypes as C
+import functools
 import math
 import os
 
@@ -113,6 +109,25 @@ class GradSync:
         for key in self.ORDER:
             self.launch(key)
         self.wait()
+
+
+# An iteration (TrainStep._iteration), described or captured.  FROZEN: bench.py, tools/exp_defer_dec.py and tools/exp_cumask.py read
+# ts.graphs[(zero, opt)][0][0] as the 4-tuple ("late", head graph | None, chain, _) and every chain entry as the 4-tuple (main graph,
+# late graph, key, slice graph | None) -- hence these field orders, the one-pair list around the Iteration, and no fifth field: whether
+# a bucket's all-reduce follows is the same for all of them (a closing iteration of a multi-GPU run) and TrainStep._run derives it.
+# They also read ts.tail_probe, late_stream, late_stream_factory, late_wgrad, sync, dist_active, plan, _forward_and_loss_partials and
+# _loss_backward; tests/test_gpu_dropout.py reads set(ts.graphs).
+Iteration = collections.namedtuple("Iteration", "kind head chain tail")
+Bucket = collections.namedtuple("Bucket", "main late key slice")
+
+
+class _Piece(list):
+    """Calls that enqueue kernels back to back on one stream.  An eager iteration replays them as they are, a captured one replays
+    the graph made from them."""
+
+    def replay(self):
+        for fn in self:
+            fn()
 
 
 class TrainState:
@@ -236,11 +251,10 @@ class TrainStep:
         self.world = self.sync.world
         self.dist_active = self.sync.active
         model.rng_rank = dist.get_rank(group) if dist.is_initialized() else 0
-        # graph step: the weight gradients of every backward segment run as graphs of their own on a second stream, next to the
-        # following segment's latency-bound chain; the decoder's streaming kernels with fewer workgroups (the plan sizes their
-        # partial-copy buffers accordingly)
-        from .engine import LATE_WGRAD, W3_LATE_WGS
-        self.late_wgrad = bool(LATE_WGRAD and use_graph)
+        # a captured step always uses the late stream (_iteration), an eager step never: there the decoder's streaming weight-gradient
+        # kernels run with fewer workgroups (the plan sizes their partial-copy buffers accordingly)
+        from .engine import W3_LATE_WGS
+        self.late_wgrad = bool(use_graph)
         model.w3_total_wgs = W3_LATE_WGS if self.late_wgrad else None
         model.__dict__["_need_grad"] = True
         self.plan = model._plan_for(x)
@@ -276,7 +290,7 @@ class TrainStep:
         if self.skip_nonfinite and self.state.gate is None:
             self.state.gate = torch.zeros(8, dtype=torch.int32, device=self.dev)
             self.state.gate[2] = self.state.step_count          # committed steps so far (a continued TrainState)
-            if getattr(self.state, "ema", None) is not None:
+            if self.state.ema is not None:
                 self.state.ema_base = self.state.step_count - self.state.ema_n
 
     # ------------------------------------------------------------------ skip_nonfinite: what the device decided (one sync per read)
@@ -305,7 +319,7 @@ class TrainStep:
     def ema_updates(self):
         """EMA updates since it was created or restored = the optimizer steps committed since then (skip_nonfinite: read from the
         device, one sync, as committed_steps); None without ema_decay."""
-        if getattr(self, "ema", None) is None:
+        if self.ema is None:
             return None
         return self.ema_n if self.gate is None else int(self.gate[2]) - self.ema_base
 
@@ -365,7 +379,11 @@ class TrainStep:
         self.epoch_iter = 0
 
     # ------------------------------------------------------------------ pieces of one step
-    _depth_mode, _berhu_thresh = "smooth_l1", None      # (class defaults: the CPU control-flow tests build the object by hand)
+    # (class defaults of what is optional: the CPU control-flow tests build the object by hand, tests/trainstep_stub.py)
+    _depth_mode, _berhu_thresh, skip_nonfinite = "smooth_l1", None, False
+    grad_hook = None               # tests: called with each bucket's key where that bucket's gradients have become final
+    tail_probe = None              # bench.py: a list to collect the main stream's (start, end) events of its wait for the late stream
+    late_stream_factory = None     # tools: what makes the late stream instead of torch.cuda.Stream
 
     def _depth_fwd(self, pred, tgt, i):
         """Level i's loss partials into acc[4i:4i+3] = (sum, count, sum d^2) -- BerHu: (-, count, sum d^2) and maxbits[i]."""
@@ -425,14 +443,14 @@ class TrainStep:
                                               self.H * self.W, self.acc.data_ptr() + 96, None, LOSS_W[3] * scale,
                                               p.seg_grad_in.data_ptr(), st()), "crd_ce_focal_bwd")
 
-    def _dgn(self, key=None, gated=False, clipped=False):
+    def _dgn(self, key=None):
         """crd_dgn_desc of one optimizer call (by reference, for the library).  key: only the tensors of that gradient bucket (its slice
-        of the norm parts and block tables + its `active` mask; the per-tensor buffers stay whole).  gated / clipped: with the verdict
-        words / the clipping buffers.  Always under hp: the scalar hyper-parameters stay 0, the kernels read w_n / decay / base /
-        warm-up of the EMA from it."""
+        of the norm parts and block tables + its `active` mask; the per-tensor buffers stay whole).  With the verdict words under
+        skip_nonfinite and the clipping buffers under max_grad_norm.  Always under hp: the scalar hyper-parameters stay 0, the kernels
+        read w_n / decay / base / warm-up of the EMA from it."""
         m = self.model
         b0, nb, mask = (0, self.nblk, self.trainable_mask) if key is None else self.opt_parts[key]
-        ema = getattr(self, "ema", None)
+        gated, clipped, ema = self.skip_nonfinite, self.max_grad_norm is not None, self.ema
         return C.byref(dgn_desc(
             p=m.flat, g=m.flat_grad, exp_avg=self.m, exp_avg_sq=self.v, prev_grad=self.pg, exp_grad_norm=self.egn, factor=self.fac,
             parts=(self.parts if clipped else self.nsq).data_ptr() + 4 * b0, parts_stride=self.nblk if clipped else 0, seg_off=self.seg,
@@ -442,79 +460,85 @@ class TrainStep:
             ema_warmup=int(self.ema_warmup) if ema is not None else 0, ema_base=self.ema_base if ema is not None and gated else 0))
 
     def _optimizer(self, key=None):
-        """key: only the tensors of that gradient bucket (block-table slice + `active` mask)."""
+        """The default step's whole optimizer.  key: only the tensors of that gradient bucket (block-table slice + `active` mask)."""
         L.check(self.lib.crd_diffgradnorm_step(self._dgn(key), L.stream()), "crd_diffgradnorm_step")
         # the bucket's new weights in the kernels' bf16 layouts, right behind its update (late stream: under the encoder's
         # backward) instead of one 169-us launch at the head of the next forward
         lo, hi = (None, None) if key is None else self.sync.ranges[key]
         self.plan.pack(lo, hi)
 
-    # skip_nonfinite pieces: the flag captures around the backward, the gated norm (per bucket or all) and the gated commit
     def _capture_flags(self, window):
+        """skip_nonfinite: the flag captures around the backward."""
         L.check(self.lib.crd_nonfinite_capture(self.gate.data_ptr() + 4 if window else None, L.stream()), "crd_nonfinite_capture")
 
-    def _norm_gated(self, key=None):
-        L.check(self.lib.crd_diffgradnorm_norm(self._dgn(key, gated=True), L.stream()), "crd_diffgradnorm_norm")
-
-    def _commit_gated(self):
-        """Every tensor's scalar and update, or none of them, then the re-pack of all weights (of unchanged ones after a skip: the
-        packed forms are a function of the fp32 parameters, so re-packing them writes the same bits)."""
-        L.check(self.lib.crd_diffgradnorm_commit(self._dgn(gated=True), L.stream()), "crd_diffgradnorm_commit")
-        self.plan.pack()
-
-    # max_grad_norm pieces: the norm pass that also writes the parts of the global norm (per bucket or all; gated with
-    # skip_nonfinite), and the commit: total + coefficient, every tensor's scalar and update, the re-pack
-    def _norm_clip(self, key=None):
-        L.check(self.lib.crd_diffgradnorm_norm(self._dgn(key, gated=self.skip_nonfinite, clipped=True), L.stream()), "crd_diffgradnorm_norm")
-
-    def _commit_clip(self):
-        L.check(self.lib.crd_diffgradnorm_commit(self._dgn(gated=self.skip_nonfinite, clipped=True), L.stream()), "crd_diffgradnorm_commit")
-        self.plan.pack()
-
+    @property
     def _deferred(self):
-        """(norm pass, commit) when the optimizer step waits for a global decision -- skip_nonfinite's verdict, max_grad_norm's
-        norm -- or None: the default step, whose buckets update as soon as their gradients are final."""
-        if getattr(self, "max_grad_norm", None) is not None:
-            return self._norm_clip, self._commit_clip
-        if getattr(self, "skip_nonfinite", False):
-            return self._norm_gated, self._commit_gated
-        return None
+        """The optimizer step waits for a global decision -- skip_nonfinite's verdict, max_grad_norm's norm: a norm pass (per bucket
+        or all) and one commit behind the last bucket, instead of the default step's buckets that update as soon as their gradients
+        are final."""
+        return self.skip_nonfinite or self.max_grad_norm is not None
 
-    def _segments(self):
-        """The iteration as a list of (callable, bucket-to-launch-after | None | 'loss' | 'gate'), for the current
-        (self._zero, self._opt): zero the gradients first / all-reduce and run the optimizer last.  skip_nonfinite: the backward is
-        bracketed by flag captures, then the gated norm ('gate': the ranks combine their verdicts here) and the gated commit.
-        max_grad_norm: the norm pass and the commit follow the whole backward (and its all-reduce) the same way."""
-        skip = getattr(self, "skip_nonfinite", False)
-        deferred = self._deferred()
-        segs = [(self._forward_and_loss_partials, "loss")]
-        first = True
+    def _norm(self, key=None):
+        """The deferred step's norm pass: finiteness test included under skip_nonfinite, the parts of the global norm written under
+        max_grad_norm."""
+        L.check(self.lib.crd_diffgradnorm_norm(self._dgn(key), L.stream()), "crd_diffgradnorm_norm")
+
+    def _commit(self):
+        """max_grad_norm: total + coefficient; then every tensor's scalar and update, or -- skip_nonfinite -- none of them; then the
+        re-pack of all weights (of unchanged ones after a skip: the packed forms are a function of the fp32 parameters, so re-packing
+        them writes the same bits)."""
+        L.check(self.lib.crd_diffgradnorm_commit(self._dgn(), L.stream()), "crd_diffgradnorm_commit")
+        self.plan.pack()
+
+    def _iteration(self, late):
+        """THE order of one iteration, for the current (self._zero, self._opt): zero the gradients first / all-reduce and run the
+        optimizer last.  Every piece is a _Piece: calls that enqueue kernels back to back on one stream.
+
+        One step = zero grads -> forward -> masked losses -> backward -> (gradient all-reduce) -> diffGradNorm, entirely as HIP
+        kernels with static buffers, so the step is captured once into HIP graphs and replayed; the host only updates the
+        hyper-parameter floats per step (OneCycleLR drives lr and beta1 every iteration, runner.py:151-152,270).
+
+        head   forward + loss partials.  Multi-GPU: the loss all-reduce follows (_reduce_loss_partials), which makes the masked-mean
+               denominators global and so reproduces the reference's loss over the gathered batch exactly.
+        chain  one Bucket per entry of GradSync.ORDER, the gradient buckets in the order the backward finishes them:
+               main   on the first bucket skip_nonfinite's flag capture (what the forward's loss sums dropped is not the window's
+                      business) and the loss backward; then the bucket's backward segment.
+               late   (late=True: a captured step) the segment's weight gradients, which nothing in the backward waits for, on a
+                      second stream next to the following segment's latency-bound chain.
+               slice  (late=True, closing iteration of a window) the bucket's optimizer slice behind the late piece, where its
+                      gradients are final -- or, deferred, its slice of the norm pass.
+               Multi-GPU, closing iteration: the bucket's SUM all-reduce follows the piece that finishes its gradients -- late: on the
+               late stream, waited for there, before the slice (the update of the decoder's parameters overlaps the encoder's
+               backward, only the last bucket's slice is exposed); eager: launched asynchronously, all waited for behind the last.
+        tail   (before, after) on the main stream, behind every bucket: skip_nonfinite's flag capture of the window; the norm pass if
+               the slices have not run it; the commit, or the default step's whole optimizer (eager).  Multi-GPU skip_nonfinite: the
+               ranks agree on the verdict (_agree) between `before` and the commit, which is then alone in `after`.
+
+        main stream:  [forward, loss] [decoder backward] [enc3+enc2 backward] [enc1] [enc0]                 [tail]
+        late stream:                                    [decoder weight grads, slice][enc3+enc2 ...]  ...  [enc0 ...]
+        (branches of ONE captured graph do not run concurrently on this stack; separate graphs on two streams do)"""
+        skip, deferred, opt = self.skip_nonfinite, self._deferred, self._opt
+        bind = functools.partial
+        chain = []
         for key in GradSync.ORDER:
-            def run(key=key, first=first):
-                if first:
-                    if skip:
-                        self._capture_flags(False)     # what the forward's loss sums dropped is not the window's business
-                    self._loss_backward()
-                self.plan.backward(tags=key)
-                if skip and not self.plan.split_late and getattr(self, "grad_hook", None) is not None:
-                    self.grad_hook(key)
-            segs.append((run, key if self._opt else None))
-            first = False
-        if deferred is not None:
-            norm, commit = deferred
-            if skip:
-                def tail(opt=self._opt):
-                    self._capture_flags(True)
-                    if opt:
-                        norm()
-                segs.append((tail, "gate" if self._opt and self.dist_active else None))
-            elif self._opt:
-                segs.append((norm, None))
-            if self._opt:
-                segs.append((commit, None))
-        elif self._opt:
-            segs.append((self._optimizer, None))
-        return segs
+            main = _Piece([bind(self.plan.backward, tags=key)])
+            if not chain:
+                main[:0] = ([bind(self._capture_flags, False)] if skip else []) + [self._loss_backward]
+            # tests: grad_hook runs (captured) where this bucket's gradients have become final
+            hook = [bind(self.grad_hook, key)] if skip and self.grad_hook is not None else []
+            if late:
+                chain.append(Bucket(main, _Piece([bind(self.plan.run_late, key)] + hook), key,
+                                    _Piece([bind(self._norm if deferred else self._optimizer, key)]) if opt else None))
+            else:
+                chain.append(Bucket(_Piece(main + hook), None, key, None))
+        before, after = _Piece([bind(self._capture_flags, True)] if skip else []), _Piece()
+        if opt and deferred:
+            if not late:
+                before.append(self._norm)
+            (after if skip and self.dist_active else before).append(self._commit)
+        elif opt and not late:
+            before.append(self._optimizer)
+        return Iteration("late" if late else "eager", _Piece([self._forward_and_loss_partials]), chain, (before, after))
 
     def _variants(self):
         k = self.update_interval
@@ -535,8 +559,9 @@ class TrainStep:
         s.wait_stream(torch.cuda.current_stream())
         self._zero, self._opt = True, True
         with torch.cuda.stream(s):
-            for fn, _ in self._segments():
-                fn()
+            it = self._iteration(late=False)       # (every piece, no collective)
+            for piece in [it.head] + [b.main for b in it.chain] + list(it.tail):
+                piece.replay()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         if self.plan.fp8_grad_layers:
@@ -545,101 +570,45 @@ class TrainStep:
             # starts by turning the previous pass's amax into the scales it quantises with (engine: crd_fp8_scale_update)
             self.plan.fp8_jit = False
         self.graphs = {}
-        if self.late_wgrad:
-            self.plan.split_late = True
-            self.late_stream = (getattr(self, "late_stream_factory", None) or torch.cuda.Stream)()
+        self.plan.split_late = True
+        self.late_stream = (self.late_stream_factory or torch.cuda.Stream)()
         for zero, opt in self._variants():
             self._zero, self._opt = zero, opt
-            self.graphs[(zero, opt)] = self._capture_variant()
+            self._capture_iteration()
         torch.cuda.synchronize()
         for t, sv in zip(keep, saved):
             t.copy_(sv)
         self.plan.packed_version = None        # the warm-up iteration packed ITS updated weights
 
-    def _capture_variant(self):
-        graphs = []
-        opt = self._opt
-        if self.late_wgrad:
-            # main stream:  [forward, loss] [decoder backward] [enc3+enc2 backward] [enc1] [enc0]            [optimizer]
-            # late stream:                                    [decoder weight grads][enc3+enc2 ...]  ...  [enc0 ...]
-            # (branches of ONE captured graph do not run concurrently on this stack; separate graphs on two streams do).
-            # Multi-GPU: the loss all-reduce follows the first graph, and each bucket's gradient all-reduce is enqueued
-            # behind its late graph (last iteration of an accumulation window only).
-            # skip_nonfinite: the late graphs and the per-bucket slices only run the gated norm (finiteness test included); the
-            # flag capture, the commit of every bucket and the re-pack follow the LAST bucket, on the main stream (tail graphs);
-            # max_grad_norm: the same order (the slices write the parts of the global norm), one shared tail with skip_nonfinite
-            skip = self.skip_nonfinite
-            deferred = self._deferred()
-            segs = self._segments()
-            main = torch.cuda.current_stream()
-            bsegs = segs[1:1 + len(GradSync.ORDER)]
-            keys = list(GradSync.ORDER)
-            g0 = None
-            mains = []
-            if self.dist_active:
-                g0 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g0):
-                    segs[0][0]()
-            for i, (fn, _) in enumerate(bsegs):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    if i == 0 and g0 is None:
-                        segs[0][0]()
-                    fn()
-                mains.append(g)
-            chain = []                                       # [(main graph, late graph, bucket key, optimizer-slice graph)]
-            for g, key in zip(mains, keys):
-                gl = torch.cuda.CUDAGraph()
-                self.late_stream.wait_stream(main)
-                with torch.cuda.graph(gl, stream=self.late_stream):
-                    self.plan.run_late(key)
-                    if skip and getattr(self, "grad_hook", None) is not None:
-                        self.grad_hook(key)         # tests: runs (captured) where this bucket's gradients have become final
-                    if opt and not self.dist_active:    # this bucket's gradients are final: its optimizer slice follows at once
-                        deferred[0](key) if deferred else self._optimizer(key)
-                gopt = None
-                if opt and self.dist_active:
-                    # multi-GPU: the bucket's optimizer slice is a graph of its own, replayed on the late stream behind THAT
-                    # bucket's all-reduce (step()), so that the update of the decoder's parameters overlaps the encoder's
-                    # backward and only the last bucket's slice is exposed
-                    gopt = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gopt, stream=self.late_stream):
-                        deferred[0](key) if deferred else self._optimizer(key)
-                main.wait_stream(self.late_stream)
-                chain.append((g, gl, key, gopt))
-            tail = None
-            if deferred:                                     # (the flag capture + commit, and -- multi-GPU -- the commit after the ranks agree)
-                agree = skip and self.dist_active
-                gt = gc = None
-                if skip or (opt and not agree):
-                    gt = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gt):
-                        if skip:
-                            self._capture_flags(True)
-                        if opt and not agree:
-                            deferred[1]()
-                if opt and agree:
-                    gc = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gc):
-                        deferred[1]()
-                if gt is not None or gc is not None:
-                    tail = (gt, gc)
-            return [(("late", g0, chain, tail), None)]
-        if not self.dist_active:      # no collective between the segments: the whole step is one graph (five fewer launches)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for fn, _ in self._segments():
-                    fn()
-            return [(g, None)]
-        for fn, after in self._segments():
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            graphs.append((g, after))
-        return graphs
+    def _capture_iteration(self):
+        """self.graphs[current variant] <- its _iteration with the pieces captured into graphs: the head as a graph of its own only
+        where a collective follows it (multi-GPU), else at the front of the first bucket's; per bucket a main graph, a late graph
+        and -- where that bucket's all-reduce comes between them (multi-GPU) -- the slice as a graph of its own, else at the end of
+        the late graph; the tail's two halves."""
+        it = self._iteration(late=True)
+        main, late = self._current_stream(), self.late_stream
+        head = self._graph(it.head) if self.dist_active else None
+        mains = [self._graph(b.main if head is not None or i else it.head + b.main) for i, b in enumerate(it.chain)]
+        chain = []
+        for gm, b in zip(mains, it.chain):
+            own = b.slice is not None and self.dist_active
+            self._stream_wait(late, main)
+            gl = self._graph(b.late + (b.slice if b.slice is not None and not own else []), late)
+            gs = self._graph(b.slice, late) if own else None
+            self._stream_wait(main, late)
+            chain.append(Bucket(gm, gl, b.key, gs))
+        tail = tuple(self._graph(piece) if piece else None for piece in it.tail)
+        self.graphs[(self._zero, self._opt)] = [(Iteration("late", head, chain, tail), None)]
 
-    # stream plumbing of the late-stream replay, as methods so that the CPU control-flow test (tests/test_ddp_cpu.py, gloo world 2)
-    # can run the very same _replay_late with stand-ins for the HIP graphs and streams
+    # graphs and streams as methods, so that the CPU control-flow tests run the very same capture and replay with stand-ins for them
+    @staticmethod
+    def _graph(fns, stream=None):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=stream):
+            for fn in fns:
+                fn()
+        return g
+
     @staticmethod
     def _current_stream():
         return torch.cuda.current_stream()
@@ -652,41 +621,46 @@ class TrainStep:
     def _on_stream(stream):
         return torch.cuda.stream(stream)
 
-    def _replay_late(self, g, opt):
-        """One iteration of the late-stream variant (see _capture_variant): per backward segment its main graph, then -- on the late
-        stream, behind it -- the segment's weight-gradient graph, and on the closing iteration of a window of a multi-GPU run that
-        bucket's all-reduce and optimizer slice, while the main stream already runs the next segment."""
-        _, g0, chain, go = g
-        main = self._current_stream()
-        if g0 is not None:
-            g0.replay()
+    def _run(self, it):
+        """One iteration, eager (the _iteration itself) or captured (_capture_iteration): the host's side of the order stated in
+        _iteration -- the replays, the two streams and the collectives."""
+        late, reduce = it.kind == "late", self._opt and self.dist_active
+        if it.head is not None:
+            it.head.replay()
+        if self.dist_active:
             self._reduce_loss_partials()       # global loss denominators (BerHu: and maxima) before the backward
-        for gm, gl, key, gopt in chain:
-            with trace.range("main:" + "+".join(key)):
-                gm.replay()
-            self._stream_wait(self.late_stream, main)
-            with self._on_stream(self.late_stream), trace.range("late:" + "+".join(key)):
-                gl.replay()
-                if self.dist_active and opt:
-                    self.sync.launch(key)      # this bucket's all-reduce, behind the graph that finishes its gradients
-                    self.sync.wait()           # (the LATE stream waits for it; the main stream runs on)
-                    gopt.replay()              # ... and the bucket's optimizer slice follows at once
-        probe = getattr(self, "tail_probe", None)
-        if probe is not None:                  # bench.py: how long the main stream idles behind the late stream at the end of an iteration
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(main)
-        self._stream_wait(main, self.late_stream)
-        if probe is not None:
-            e1.record(main)
-            probe.append((e0, e1))
-        if isinstance(go, tuple):              # skip_nonfinite: flag capture (+ commit); multi-GPU: the ranks agree, then the commit
-            if go[0] is not None:              # (max_grad_norm alone: the commit)
-                go[0].replay()
-            if go[1] is not None:
-                self._agree()
-                go[1].replay()
-        elif go is not None:
-            go.replay()
+        if late:
+            main = self._current_stream()
+        for b in it.chain:
+            with trace.range("main:" + "+".join(b.key)):
+                b.main.replay()
+            if late:
+                self._stream_wait(self.late_stream, main)
+                with self._on_stream(self.late_stream), trace.range("late:" + "+".join(b.key)):
+                    b.late.replay()
+                    if reduce:
+                        self.sync.launch(b.key)    # this bucket's all-reduce, behind the graph that finishes its gradients
+                        self.sync.wait()           # (the LATE stream waits for it; the main stream runs on)
+                        b.slice.replay()           # ... and the bucket's optimizer slice follows at once
+            elif reduce:
+                self.sync.launch(b.key)
+        if late:
+            probe = self.tail_probe
+            if probe is not None:              # bench.py: how long the main stream idles behind the late stream at the end of an iteration
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(main)
+            self._stream_wait(main, self.late_stream)
+            if probe is not None:
+                e1.record(main)
+                probe.append((e0, e1))
+        elif reduce:
+            self.sync.wait()
+        before, after = it.tail
+        if before:
+            before.replay()
+        if after:
+            self._agree()
+            after.replay()
 
     def _agree(self):
         """Multi-GPU skip_nonfinite: every rank skips or commits together.  Non-finite gradient elements reach every rank through
@@ -708,7 +682,7 @@ class TrainStep:
         if tuple(p.requires_grad for p in self._params) != self._frozen_sig:
             raise L.CrdError("camradepth_amd.TrainStep: requires_grad of a parameter changed after the step was built (its plan "
                              "and optimizer mask are fixed at construction): build a new TrainStep")
-        ema = getattr(self, "ema", None) is not None
+        ema = self.ema is not None
         if ema and self._ema_swapped:
             raise L.CrdError("camradepth_amd.TrainStep.step() inside ema_weights(): the parameters are the averaged weights there; "
                              "leave the context before training on")
@@ -728,11 +702,11 @@ class TrainStep:
             if ema:
                 # [5] w_n of this update as the host counts it (the ungated kernels); [6], [7], [15]: decay, base and warm-up, from
                 # which the gated commit forms w_n for the device's own count (include/camradepth_hip.h, crd_dgn_desc)
-                if not getattr(self, "skip_nonfinite", False):
+                if not self.skip_nonfinite:
                     self.ema_n += 1
                 hp_host[5], hp_host[6] = ema_weight(self.ema_decay, self.ema_warmup, max(self.ema_n, 1))[1], self.ema_decay
                 hp_host.view(torch.int32)[7], hp_host.view(torch.int32)[15] = self.ema_base, 1 if self.ema_warmup else 0
-            if getattr(self, "skip_nonfinite", False):
+            if self.skip_nonfinite:
                 hp_host.view(torch.float64)[4:7] = torch.tensor([lr, b1, b2], dtype=torch.float64)
                 hp_host.view(torch.int32)[14] = self.step_count
                 self.hp.copy_(hp_host, non_blocking=True)
@@ -743,27 +717,8 @@ class TrainStep:
             self._zero, self._opt = zero, opt
         self.plan.ensure_packed()              # first step / parameters written from outside since the last one
         if self.use_graph and (zero, opt) not in self.graphs:      # e.g. a flush right after an update (last_of_epoch)
-            self.graphs[(zero, opt)] = self._capture_variant()
-        runs = self.graphs[(zero, opt)] if self.use_graph else [(None, a) for _, a in self._segments()]
-        fns = None if self.use_graph else [f for f, _ in self._segments()]
-        for i, (g, after) in enumerate(runs):
-            if isinstance(g, tuple):           # ("late", first graph, [(main graph, late graph, bucket, optimizer slice)], -)
-                self._replay_late(g, opt)
-            elif g is not None:
-                with trace.range("graph:%d" % i):
-                    g.replay()
-            else:
-                with trace.range("segment:%d" % i):
-                    fns[i]()
-            if after == "loss":
-                if self.dist_active:
-                    self._reduce_loss_partials()
-            elif after == "gate":
-                self._agree()
-            elif after is not None and self.dist_active:
-                self.sync.launch(after)
-                if after == GradSync.ORDER[-1]:
-                    self.sync.wait()
+            self._capture_iteration()
+        self._run(self.graphs[(zero, opt)][0][0] if self.use_graph else self._iteration(late=False))
         if self.dist_active and self._depth_mode == "berhu":
             dist.all_reduce(self.berhu_acc, group=self.sync.group)     # BerHu's loss sums (phase b runs in the backward): losses() only
         if opt:                                # every bucket was re-packed behind its optimizer slice

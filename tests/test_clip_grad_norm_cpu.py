@@ -4,7 +4,6 @@ is built; and in a gloo world of two both ranks take the clipped path in the sam
 no more (the HIP pieces replaced by stand-ins as in tests/test_skip_nonfinite_cpu.py)."""
 import os
 import socket
-import types
 
 import pytest
 import torch
@@ -13,80 +12,51 @@ import torch.multiprocessing as mp
 
 from camradepth_amd import lib as L
 from camradepth_amd.optim import check_max_grad_norm, diffGradNorm
-from camradepth_amd.trainer import GradSync, TrainStep
+from camradepth_amd.trainer import GradSync
+from tests.trainstep_stub import eager_order, record_pieces as _record, stub_model as _model, stub_trainstep
 
 
 def _stand_in(m, skip, clip, dist_active, k=1, world=1):
-    ts = object.__new__(TrainStep)
-    ts.state = types.SimpleNamespace(max_grad_norm=clip)
-    ts.model, ts.sync = m, GradSync(m)
-    ts.dist_active, ts.world, ts.update_interval, ts.use_graph, ts.graphs = dist_active, world, k, False, None
-    ts.schedule, ts.lr, ts.betas, ts.eps, ts.wd = None, 1e-3, (0.9, 0.999), 1e-8, 0.0
-    ts.iter_count = ts.epoch_iter = ts.sched_steps = ts.step_count = 0
-    ts._window_open, ts._window_pos, ts._zero, ts._opt = False, 0, True, True
-    ts.hp, ts.hp_ring, ts.acc = torch.zeros(16), [torch.zeros(16) for _ in range(4)], torch.zeros(16, dtype=torch.int64)
-    ts.gate = torch.zeros(8, dtype=torch.int32) if skip else None
-    ts.skip_nonfinite = skip
-    ts.plan = types.SimpleNamespace(ensure_packed=lambda: None, packed_version=None, split_late=False, backward=lambda tags=None: None)
-    ts._params, ts._frozen_sig = [], ()
-    return ts
-
-
-def _model():
-    from camradepth_amd.model import CamRaDepth
-    m = CamRaDepth(input_channels=7, depths=(1, 1, 1, 1))
-    m._ensure_grad_views()
-    return m
-
-
-def _record(ts, calls):
-    ts._forward_and_loss_partials = lambda: calls.append("fwd")
-    ts._loss_backward = lambda: calls.append("loss_bwd")
-    ts.plan.backward = lambda tags=None: calls.append("bwd:" + "+".join(tags))
-    ts._capture_flags = lambda window: calls.append("capture:%s" % ("window" if window else "start"))
-    ts._norm_gated = lambda key=None: calls.append("norm_gated:%s" % (key,))
-    ts._commit_gated = lambda: calls.append("commit_gated")
-    ts._norm_clip = lambda key=None: calls.append("norm_clip:%s" % (key,))
-    ts._commit_clip = lambda: calls.append("commit_clip")
-    ts._optimizer = lambda key=None: calls.append("optimizer:%s" % (key,))
-
-
-def _order(ts):
-    calls = []
-    _record(ts, calls)
-    for fn, _ in ts._segments():
-        fn()
-    return calls
+    return stub_trainstep(m, skip=skip, clip=clip, dist_active=dist_active, k=k, world=world)
 
 
 BWD = ["bwd:dec", "bwd:enc3+enc2", "bwd:enc1", "bwd:enc0"]
 
 
+def _pieces(calls):
+    return [c for c in calls if isinstance(c, str) and c not in ("loss", "wait", "gate")]
+
+
 def test_segment_order_without_and_with_the_switch():
     m = _model()
     for dist_active in (False, True):
+        # the host's collectives of a distributed run: the loss all-reduce, each bucket's launch, the wait, the agreement point
+        def hosts(calls):
+            return [c for c in calls if c not in _pieces(calls)]
+        closing = ["loss"] + list(GradSync.ORDER) + ["wait"] if dist_active else []
         ts = _stand_in(m, False, None, dist_active)
-        assert [a for _, a in ts._segments()] == ["loss"] + list(GradSync.ORDER) + [None]
-        assert ts._segments()[-1][0] == ts._optimizer
-        assert _order(ts) == ["fwd", "loss_bwd"] + BWD + ["optimizer:None"]
+        calls = eager_order(ts)
+        assert hosts(calls) == closing
+        assert ts._iteration(late=False).tail == ([ts._optimizer], [])
+        assert _pieces(calls) == ["fwd", "loss_bwd"] + BWD + ["optimizer:None"]
         ts = _stand_in(m, False, 1.0, dist_active)
-        segs = ts._segments()
-        assert [a for _, a in segs] == ["loss"] + list(GradSync.ORDER) + [None, None]
-        assert segs[-2][0] == ts._norm_clip and segs[-1][0] == ts._commit_clip
-        assert ts._optimizer not in [f for f, _ in segs]
-        assert _order(ts) == ["fwd", "loss_bwd"] + BWD + ["norm_clip:None", "commit_clip"]
+        calls = eager_order(ts)
+        assert hosts(calls) == closing
+        assert ts._iteration(late=False).tail == ([ts._norm, ts._commit], [])
+        assert _pieces(calls) == ["fwd", "loss_bwd"] + BWD + ["norm:None", "commit"] and calls[-2:] == ["norm:None", "commit"]
         ts._opt = False                                  # an accumulating iteration: no norm, no commit -- the default segments
-        assert [a for _, a in ts._segments()] == ["loss"] + [None] * len(GradSync.ORDER)
-        assert _order(ts) == ["fwd", "loss_bwd"] + BWD
+        calls = eager_order(ts)
+        assert hosts(calls) == (["loss"] if dist_active else []) and ts._iteration(late=False).tail == ([], [])
+        assert _pieces(calls) == ["fwd", "loss_bwd"] + BWD
         # both switches: skip_nonfinite's tail (flag capture, gated norm, agreement point) runs the clipping pieces
         ts = _stand_in(m, True, float("inf"), dist_active)
-        segs = ts._segments()
-        assert [a for _, a in segs] == ["loss"] + list(GradSync.ORDER) + (["gate"] if dist_active else [None]) + [None]
-        assert segs[-1][0] == ts._commit_clip
-        assert _order(ts) == ["fwd", "capture:start", "loss_bwd"] + BWD + ["capture:window", "norm_clip:None", "commit_clip"]
+        calls = eager_order(ts)
+        assert hosts(calls) == (closing + ["gate"] if dist_active else [])
+        assert calls[-3:] == (["norm:None", "gate", "commit"] if dist_active else ["capture:window", "norm:None", "commit"])
+        assert _pieces(calls) == ["fwd", "capture:start", "loss_bwd"] + BWD + ["capture:window", "norm:None", "commit"]
         # skip_nonfinite alone is unchanged
         ts = _stand_in(m, True, None, dist_active)
-        assert _order(ts) == ["fwd", "capture:start", "loss_bwd"] + BWD + ["capture:window", "norm_gated:None", "commit_gated"]
+        assert _pieces(eager_order(ts)) == ["fwd", "capture:start", "loss_bwd"] + BWD + ["capture:window", "norm:None", "commit"]
 
 
 def test_max_grad_norm_values_are_checked():
@@ -149,11 +119,11 @@ def _worker(rank, world, port, q):
             res[clip] = (ran, calls, colls)
         ran0, calls0, colls0 = res[None]
         ran1, calls1, colls1 = res[0.5]
-        tail = ["norm_clip:None", "commit_clip"]
+        tail = ["norm:None", "commit"]
         ok = ran0 == ran1 == [False, True, False, True] and colls1 == colls0 and not ts.sync.pending
-        ok = ok and [c for c in calls1 if not c.startswith(("norm_clip", "commit_clip"))] == \
+        ok = ok and [c for c in calls1 if not c.startswith(("norm", "commit"))] == \
             [c for c in calls0 if not c.startswith("optimizer")]
-        ok = ok and calls1.count("commit_clip") == 2 and calls1[-2:] == tail and calls1[calls1.index("commit_clip") - 1] == tail[0]
+        ok = ok and calls1.count("commit") == 2 and calls1[-2:] == tail and calls1[calls1.index("commit") - 1] == tail[0]
         q.put((rank, bool(ok), calls1))
     finally:
         dist.destroy_process_group()

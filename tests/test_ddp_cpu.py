@@ -73,22 +73,10 @@ def _worker_step(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from camradepth_amd.model import CamRaDepth
-        from camradepth_amd.trainer import GradSync, TrainStep
-        m = CamRaDepth(input_channels=7, depths=(1, 1, 1, 1))
-        m._ensure_grad_views()
-        import types
-        ts = object.__new__(TrainStep)
-        ts.state = types.SimpleNamespace()          # the shape-independent half (trainer.TrainState): counters, schedule, window
-        ts.model, ts.sync = m, GradSync(m)
-        ts.dist_active, ts.world, ts.update_interval, ts.use_graph, ts.graphs = True, world, 2, False, None
-        ts.schedule, ts.lr, ts.betas, ts.eps, ts.wd = None, 1e-3, (0.9, 0.999), 1e-8, 0.0
-        ts.iter_count = ts.epoch_iter = ts.sched_steps = ts.step_count = 0
-        ts._window_open, ts._window_pos, ts._zero, ts._opt = False, 0, True, True
-        ts.hp, ts.hp_ring, ts.acc = torch.zeros(8), [torch.zeros(8) for _ in range(4)], torch.zeros(16, dtype=torch.int64)
-        import types
-        ts.plan = types.SimpleNamespace(ensure_packed=lambda: None, packed_version=None)     # (the weight packing is a HIP segment too)
-        ts._params, ts._frozen_sig = [], ()
+        from camradepth_amd.trainer import GradSync
+        from tests.trainstep_stub import stub_model, stub_trainstep
+        m = stub_model()
+        ts = stub_trainstep(m, dist_active=True, k=2, world=world)
         seen, accs = [], []
 
         def fwd():
@@ -105,10 +93,9 @@ def _worker_step(rank, world, port, q):
         def optim():
             seen.append(m.flat_grad.clone())
 
-        def segments():
-            segs = [(fwd, "loss")] + [((lambda k=k: bwd(k)), k if ts._opt else None) for k in GradSync.ORDER]
-            return segs + ([(optim, None)] if ts._opt else [])
-        ts._segments = segments
+        ts._forward_and_loss_partials, ts._loss_backward = fwd, lambda: None
+        ts.plan.backward = lambda tags=None: bwd(tags)
+        ts._optimizer = lambda key=None: optim()
         ran = []
         for it in range(5):
             ran.append(ts.step(last_of_epoch=(it == 4)))
@@ -139,31 +126,20 @@ def test_train_step_control_flow_world2():
 
 
 def _worker_late(rank, world, port, q):
-    """The LATE-STREAM distributed variant of TrainStep (trainer._capture_variant / _replay_late: per backward segment a main graph,
+    """The LATE-STREAM distributed variant of TrainStep (trainer._capture_iteration / _run: per backward segment a main graph,
     behind it on a second stream the segment's weight-gradient graph, then -- closing iteration of a window only -- that bucket's
-    all-reduce and its optimizer slice) replayed end to end through TrainStep.step(), with CPU stand-ins for the HIP graphs and
-    streams, against the single-process result computed in closed form."""
+    all-reduce and its optimizer slice) captured by the trainer's own code and replayed end to end through TrainStep.step(), with
+    CPU stand-ins for the HIP graphs and streams, against the single-process result computed in closed form."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import contextlib
-        import types
-        from camradepth_amd.model import CamRaDepth
-        from camradepth_amd.trainer import GradSync, TrainStep
+        from camradepth_amd.trainer import GradSync
+        from tests.trainstep_stub import stub_model, stub_trainstep
         torch.manual_seed(0)
-        m = CamRaDepth(input_channels=7, depths=(1, 1, 1, 1))
-        m._ensure_grad_views()
+        m = stub_model()
         p0 = m.flat.detach().clone()
-        ts = object.__new__(TrainStep)
-        ts.state = types.SimpleNamespace()
-        ts.model, ts.sync = m, GradSync(m)
-        ts.dist_active, ts.world, ts.update_interval, ts.use_graph = True, world, 2, True
-        ts.schedule, ts.lr, ts.betas, ts.eps, ts.wd = None, 1e-3, (0.9, 0.999), 1e-8, 0.0
-        ts.iter_count = ts.epoch_iter = ts.sched_steps = ts.step_count = 0
-        ts._window_open, ts._window_pos, ts._zero, ts._opt = False, 0, True, True
-        ts.hp, ts.hp_ring, ts.acc = torch.zeros(8), [torch.zeros(8) for _ in range(4)], torch.zeros(16, dtype=torch.int64)
-        ts.plan = types.SimpleNamespace(ensure_packed=lambda: None, packed_version=None)
-        ts._params, ts._frozen_sig = [], ()
+        ts = stub_trainstep(m, dist_active=True, k=2, world=world, late=True)
         ts.late_stream = "late"
         log = []
         ts._current_stream = lambda: "main"
@@ -172,36 +148,43 @@ def _worker_late(rank, world, port, q):
         launch = ts.sync.launch
         ts.sync.launch = lambda key: (log.append(("allreduce", key)), launch(key))[1]
 
-        class G:                                   # stand-in for a captured graph
-            def __init__(self, tag, fn):
-                self.tag, self.fn = tag, fn
+        class G:                                   # stand-in for a captured graph: replays the calls it was captured from
+            def __init__(self, fns):
+                self.fns = list(fns)
 
             def replay(self):
-                log.append(self.tag)
-                self.fn()
+                for fn in self.fns:
+                    fn()
+        ts._graph = lambda fns, stream=None: G(fns)
 
         LR = 0.5
 
-        def variant(zero, opt):
-            def fwd():
-                if zero:
-                    m.flat_grad.zero_()
-                ts.acc.zero_()
-                ts.acc[0] += rank + 1
-                ts.acc[1] += 1
+        def fwd():
+            log.append(("fwd",))
+            if ts._zero:
+                m.flat_grad.zero_()
+            ts.acc.zero_()
+            ts.acc[0] += rank + 1
+            ts.acc[1] += 1
 
-            def late(key):                          # the bucket's weight gradients, rank- and iteration-dependent
-                lo, hi = ts.sync.ranges[key]
-                m.flat_grad[lo:hi] += (rank + 1.0) * (ts.iter_count + 1)
+        def late(key):                          # the bucket's weight gradients, rank- and iteration-dependent
+            log.append(("late", key))
+            lo, hi = ts.sync.ranges[key]
+            m.flat_grad[lo:hi] += (rank + 1.0) * (ts.iter_count + 1)
 
-            def optim(key):                         # the bucket's optimizer slice on the REDUCED gradients
-                lo, hi = ts.sync.ranges[key]
-                with torch.no_grad():
-                    m.flat[lo:hi] -= LR * m.flat_grad[lo:hi]
-            chain = [(G(("main", key), lambda: None), G(("late", key), lambda key=key: late(key)), key,
-                      G(("opt", key), lambda key=key: optim(key)) if opt else None) for key in GradSync.ORDER]
-            return [(("late", G(("fwd",), fwd), chain, None), None)]
-        ts.graphs = {(z, o): variant(z, o) for z in (True, False) for o in (True, False)}
+        def optim(key):                         # the bucket's optimizer slice on the REDUCED gradients
+            log.append(("opt", key))
+            lo, hi = ts.sync.ranges[key]
+            with torch.no_grad():
+                m.flat[lo:hi] -= LR * m.flat_grad[lo:hi]
+        ts._forward_and_loss_partials, ts._loss_backward = fwd, lambda: None
+        ts.plan.backward = lambda tags=None: log.append(("main", tags))
+        ts.plan.run_late, ts._optimizer = late, optim
+        ts.graphs = {}
+        for ts._zero in (True, False):             # the trainer's own capture of every variant, as TrainStep._capture does
+            for ts._opt in (True, False):
+                ts._capture_iteration()
+        del log[:]                                 # (the stream edges of the capture)
         ran, accs = [], []
         for it in range(5):
             ran.append(ts.step(last_of_epoch=(it == 4)))

@@ -17,6 +17,7 @@ import torch.multiprocessing as mp
 from camradepth_amd import lib as L
 from camradepth_amd.optim import check_ema_decay, diffGradNorm, ema_weight
 from camradepth_amd.trainer import GradSync, TrainStep
+from tests.trainstep_stub import eager_order, record_pieces as _record, stub_model as _model, stub_trainstep
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("crd_diffgradnorm_norm", "crd_diffgradnorm_commit", "crd_diffgradnorm_step", "crd_swap_f32")
@@ -88,49 +89,7 @@ def test_new_symbols_are_declared_and_bound():
 
 # ---------------------------------------------------------------------------------------------- control flow (stand-ins)
 def _stand_in(m, skip, clip, ema, dist_active, k=1, world=1):
-    ts = object.__new__(TrainStep)
-    ts.state = types.SimpleNamespace(max_grad_norm=clip)
-    if ema is not None:
-        ts.state.ema, ts.state.ema_decay, ts.state.ema_warmup = torch.zeros(4), ema, True
-        ts.state.ema_n, ts.state.ema_base, ts.state._ema_swapped = 0, 0, False
-    ts.model, ts.sync = m, GradSync(m)
-    ts.dist_active, ts.world, ts.update_interval, ts.use_graph, ts.graphs = dist_active, world, k, False, None
-    ts.schedule, ts.lr, ts.betas, ts.eps, ts.wd = None, 1e-3, (0.9, 0.999), 1e-8, 0.0
-    ts.iter_count = ts.epoch_iter = ts.sched_steps = ts.step_count = 0
-    ts._window_open, ts._window_pos, ts._zero, ts._opt = False, 0, True, True
-    ts.hp, ts.hp_ring, ts.acc = torch.zeros(16), [torch.zeros(16) for _ in range(4)], torch.zeros(16, dtype=torch.int64)
-    ts.gate = torch.zeros(8, dtype=torch.int32) if skip else None
-    ts.skip_nonfinite = skip
-    ts.plan = types.SimpleNamespace(ensure_packed=lambda: None, packed_version=None, split_late=False, backward=lambda tags=None: None)
-    ts._params, ts._frozen_sig = [], ()
-    return ts
-
-
-def _model():
-    from camradepth_amd.model import CamRaDepth
-    m = CamRaDepth(input_channels=7, depths=(1, 1, 1, 1))
-    m._ensure_grad_views()
-    return m
-
-
-def _record(ts, calls):
-    ts._forward_and_loss_partials = lambda: calls.append("fwd")
-    ts._loss_backward = lambda: calls.append("loss_bwd")
-    ts.plan.backward = lambda tags=None: calls.append("bwd:" + "+".join(tags))
-    ts._capture_flags = lambda window: calls.append("capture:%s" % ("window" if window else "start"))
-    ts._norm_gated = lambda key=None: calls.append("norm_gated:%s" % (key,))
-    ts._commit_gated = lambda: calls.append("commit_gated")
-    ts._norm_clip = lambda key=None: calls.append("norm_clip:%s" % (key,))
-    ts._commit_clip = lambda: calls.append("commit_clip")
-    ts._optimizer = lambda key=None: calls.append("optimizer:%s" % (key,))
-
-
-def _order(ts):
-    calls = []
-    _record(ts, calls)
-    for fn, _ in ts._segments():
-        fn()
-    return calls
+    return stub_trainstep(m, skip=skip, clip=clip, ema=ema, dist_active=dist_active, k=k, world=world)
 
 
 def test_segment_order_is_the_same_with_and_without_ema():
@@ -140,11 +99,13 @@ def test_segment_order_is_the_same_with_and_without_ema():
             for opt in (True, False):
                 off, on = _stand_in(m, skip, clip, None, dist_active), _stand_in(m, skip, clip, 0.9, dist_active)
                 off._opt = on._opt = opt
-                assert [a for _, a in on._segments()] == [a for _, a in off._segments()]
-                assert [f.__name__ for f, _ in on._segments()] == [f.__name__ for f, _ in off._segments()]
-                assert _order(on) == _order(off)
+                names = [[[getattr(f, "__name__", None) or f.func.__name__ for f in piece] for piece in (it.head, *it.tail)]
+                         for it in (on._iteration(late=False), off._iteration(late=False))]
+                assert names[0] == names[1] and names[0][0] == ["_forward_and_loss_partials"]
+                assert eager_order(on) == eager_order(off)             # the pieces and the host's collectives between them
     ts = _stand_in(m, False, None, 0.9, False)
-    assert ts._segments()[-1][0] == ts._optimizer and len(ts._segments()) == 2 + len(GradSync.ORDER)
+    it = ts._iteration(late=False)
+    assert it.tail == ([ts._optimizer], []) and len(it.chain) == len(GradSync.ORDER)
 
 
 def test_step_uploads_the_weight_and_refuses_inside_the_swap():

@@ -187,6 +187,39 @@ def test_training_iteration_is_bit_reproducible(variant, depths, use_graph):
     assert float(ga[0].abs().sum()) > 0
 
 
+def test_captured_window_flush_and_deferred_tail_are_bit_reproducible():
+    """Every switch of the optimizer tail at once (skip_nonfinite, max_grad_norm, ema_decay) over an accumulation window of three
+    and a fourth iteration flagged last_of_epoch -- the first of a new window, so the (zero, optimizer) variant that no window of
+    three holds is captured on demand: two captured runs from the same seed end with the same bits in the parameters, the EMA
+    and the optimizer state, and hold exactly these four variants."""
+    from camradepth_amd.trainer import TrainStep
+    cfg = dataclasses.replace(ModelConfig.variant("base"), depths=(1, 1, 1, 1))
+    sd = synth.fill_state_dict({n: s for n, s in param_specs(cfg)}, 0)
+    masks = synth.make_masks(cfg, 2, seed=99)
+    batches = [{k: v.cuda() for k, v in synth.make_batch(2, 64, 96, seed=70 + i).items()} for i in range(4)]
+    runs = []
+    for _ in range(2):
+        m = build(cfg, sd)
+        ts = TrainStep(m, 2, 64, 96, lr=1e-3, update_interval=3, use_graph=True, skip_nonfinite=True, max_grad_norm=1.0, ema_decay=0.9)
+        fix_masks(ts, masks)
+        ran = []
+        for i, b in enumerate(batches):
+            ts.set_batch(b)
+            ran.append(ts.step(last_of_epoch=(i == 3)))
+        torch.cuda.synchronize()
+        assert ran == [False, False, True, True] and ts.committed_steps == 2 and ts.ema_updates == 2
+        assert set(ts.graphs) == {(True, False), (False, False), (False, True), (True, True)}
+        runs.append((m.flat.clone(), ts.ema.clone(), {n: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
+                                                      for n, st in ts.optimizer_state().items()}))
+    (pa, ea, oa), (pb, eb, ob) = runs
+    assert torch.equal(pa, pb) and torch.equal(ea, eb) and not torch.equal(pa, ea)
+    assert oa.keys() == ob.keys()
+    for n in oa:
+        for k, v in oa[n].items():
+            assert torch.equal(v, ob[n][k]) if torch.is_tensor(v) else v == ob[n][k], (n, k)
+    assert float((pa - sd_flat(m, sd)).abs().sum()) > 0
+
+
 @pytest.mark.parametrize("B,H,W", [(3, 96, 160), (1, 160, 96)])
 def test_graph_step_at_ragged_sizes_matches_eager_step(B, H, W):
     """TrainStep at frame sizes whose grids are odd multiples of the kernels' tiles (3 x 5 / 5 x 3 pixels at stage 4) and odd

@@ -176,22 +176,10 @@ MAXIMA = ((3.0, 1.0, 2.0), (1.5, 4.0, 2.5))      # per rank, per depth level: ma
 
 def _scenario(rank, world, mode, late, log, holder):
     import contextlib
-    import types
-    from camradepth_amd.model import CamRaDepth
-    from camradepth_amd.trainer import GradSync, TrainStep
-    m = CamRaDepth(input_channels=7, depths=(1, 1, 1, 1))
-    m._ensure_grad_views()
-    ts = object.__new__(TrainStep)
+    from camradepth_amd.trainer import GradSync
+    from tests.trainstep_stub import stub_model, stub_trainstep
+    ts = stub_trainstep(stub_model(), dist_active=True, k=2, world=world, late=late)
     holder["ts"] = ts
-    ts.state = types.SimpleNamespace()
-    ts.model, ts.sync = m, GradSync(m)
-    ts.dist_active, ts.world, ts.update_interval, ts.use_graph, ts.graphs = True, world, 2, late, None
-    ts.schedule, ts.lr, ts.betas, ts.eps, ts.wd = None, 1e-3, (0.9, 0.999), 1e-8, 0.0
-    ts.iter_count = ts.epoch_iter = ts.sched_steps = ts.step_count = 0
-    ts._window_open, ts._window_pos, ts._zero, ts._opt = False, 0, True, True
-    ts.hp, ts.hp_ring, ts.acc = torch.zeros(8), [torch.zeros(8) for _ in range(4)], torch.zeros(16, dtype=torch.int64)
-    ts.plan = types.SimpleNamespace(ensure_packed=lambda: None, packed_version=None)
-    ts._params, ts._frozen_sig = [], ()
     if mode == "berhu":
         ts._depth_mode, ts._berhu_thresh = "berhu", 0.2
         ts.maxbits = torch.zeros(4, dtype=torch.int32)
@@ -212,6 +200,8 @@ def _scenario(rank, world, mode, late, log, holder):
         if mode == "berhu" and key == GradSync.ORDER[0]:          # phase (b) runs at the head of the backward
             seen_c.append((ts._berhu_thresh * ts.maxbits[:3].view(torch.float32).double()).tolist())
             ts.berhu_acc[0] += rank + 1
+    ts._forward_and_loss_partials, ts._loss_backward, ts._optimizer = fwd, lambda: None, lambda key=None: None
+    ts.plan.backward = lambda tags=None: bwd(tags)
     if late:
         ts.late_stream = "late"
         ts._current_stream = lambda: "main"
@@ -219,20 +209,17 @@ def _scenario(rank, world, mode, late, log, holder):
         ts._on_stream = lambda stream: contextlib.nullcontext()
 
         class G:
-            def __init__(self, fn):
-                self.fn = fn
+            def __init__(self, fns):
+                self.fns = list(fns)
 
             def replay(self):
-                self.fn()
-
-        def variant(opt):
-            chain = [(G(lambda key=key: bwd(key)), G(lambda: None), key, G(lambda: None) if opt else None) for key in GradSync.ORDER]
-            return [(("late", G(fwd), chain, None), None)]
-        ts.graphs = {(z, o): variant(o) for z in (True, False) for o in (True, False)}
-    else:
-        def segments():
-            return [(fwd, "loss")] + [((lambda k=k: bwd(k)), k if ts._opt else None) for k in GradSync.ORDER]
-        ts._segments = segments
+                for fn in self.fns:
+                    fn()
+        ts._graph = lambda fns, stream=None: G(fns)
+        ts.graphs = {}
+        for ts._zero in (True, False):             # the trainer's own capture of every variant
+            for ts._opt in (True, False):
+                ts._capture_iteration()
     for it in range(2):
         ts.step()
     return ts, seen_c

@@ -4,65 +4,42 @@ two, one rank's local dropped-partial verdict makes BOTH ranks skip (trainer.Tra
 by stand-ins as in tests/test_ddp_cpu.py."""
 import os
 import socket
-import types
-
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from camradepth_amd.trainer import GradSync, TrainStep
+from camradepth_amd.trainer import GradSync
+from tests.trainstep_stub import eager_order, stub_model as _model, stub_trainstep
 
 
 def _stand_in(m, skip, dist_active, k=1, world=1):
-    ts = object.__new__(TrainStep)
-    ts.state = types.SimpleNamespace()
-    ts.model, ts.sync = m, GradSync(m)
-    ts.dist_active, ts.world, ts.update_interval, ts.use_graph, ts.graphs = dist_active, world, k, False, None
-    ts.schedule, ts.lr, ts.betas, ts.eps, ts.wd = None, 1e-3, (0.9, 0.999), 1e-8, 0.0
-    ts.iter_count = ts.epoch_iter = ts.sched_steps = ts.step_count = 0
-    ts._window_open, ts._window_pos, ts._zero, ts._opt = False, 0, True, True
-    ts.hp, ts.hp_ring, ts.acc = torch.zeros(16), [torch.zeros(16) for _ in range(4)], torch.zeros(16, dtype=torch.int64)
-    ts.gate = torch.zeros(8, dtype=torch.int32) if skip else None
-    ts.skip_nonfinite = skip
-    ts.plan = types.SimpleNamespace(ensure_packed=lambda: None, packed_version=None, split_late=False, backward=lambda tags=None: None)
-    ts._params, ts._frozen_sig = [], ()
-    return ts
+    return stub_trainstep(m, skip=skip, dist_active=dist_active, k=k, world=world)
 
 
-def _model():
-    from camradepth_amd.model import CamRaDepth
-    m = CamRaDepth(input_channels=7, depths=(1, 1, 1, 1))
-    m._ensure_grad_views()
-    return m
+BWD = ["bwd:dec", "bwd:enc3+enc2", "bwd:enc1", "bwd:enc0"]
 
 
 def test_gated_segment_order_only_with_the_switch():
     m = _model()
     for dist_active in (False, True):
+        def expect(first, tail, opt=True):               # the host's collectives of a distributed run between the pieces
+            if not dist_active:
+                return ["fwd"] + first + BWD + [c for c in tail if c != "gate"]
+            out = ["fwd", "loss"] + first
+            for b, key in zip(BWD, GradSync.ORDER):
+                out += [b, key] if opt else [b]
+            return out + (["wait"] if opt else []) + tail
         ts = _stand_in(m, False, dist_active)
-        segs = ts._segments()
-        assert [a for _, a in segs] == ["loss"] + list(GradSync.ORDER) + [None]
-        assert segs[-1][0] == ts._optimizer
+        assert eager_order(ts) == expect(["loss_bwd"], ["optimizer:None"])
+        assert ts._iteration(late=False).tail == ([ts._optimizer], [])
         ts = _stand_in(m, True, dist_active)
-        segs = ts._segments()
-        assert [a for _, a in segs] == ["loss"] + list(GradSync.ORDER) + (["gate"] if dist_active else [None]) + [None]
-        assert segs[-1][0] == ts._commit_gated and ts._optimizer not in [f for f, _ in segs]
+        # the pieces run in this order: capture(backward start) -> backward -> capture(window) -> gated norm -> commit
+        assert eager_order(ts) == expect(["capture:start", "loss_bwd"], ["capture:window", "norm:None", "gate", "commit"])
+        before, after = ts._iteration(late=False).tail
+        assert (before + after)[-1] == ts._commit and ts._optimizer not in before + after
+        assert after == ([ts._commit] if dist_active else [])           # the ranks agree before a commit of its own
         ts._opt = False                                  # an accumulating iteration: capture, but no norm and no commit
-        segs = ts._segments()
-        assert [a for _, a in segs] == ["loss"] + [None] * len(GradSync.ORDER) + [None]
-    # the pieces run in this order: capture(backward start) -> backward -> capture(window) -> gated norm -> commit
-    ts = _stand_in(m, True, False)
-    calls = []
-    ts._forward_and_loss_partials = lambda: calls.append("fwd")
-    ts._loss_backward = lambda: calls.append("loss_bwd")
-    ts.plan.backward = lambda tags=None: calls.append("bwd:" + "+".join(tags))
-    ts._capture_flags = lambda window: calls.append("capture:%s" % ("window" if window else "start"))
-    ts._norm_gated = lambda key=None: calls.append("norm:%s" % (key,))
-    ts._commit_gated = lambda: calls.append("commit")
-    for fn, _ in ts._segments():
-        fn()
-    assert calls == ["fwd", "capture:start", "loss_bwd", "bwd:dec", "bwd:enc3+enc2", "bwd:enc1", "bwd:enc0", "capture:window",
-                     "norm:None", "commit"]
+        assert eager_order(ts) == expect(["capture:start", "loss_bwd"], ["capture:window"], opt=False)
 
 
 def _free_port():
@@ -100,8 +77,8 @@ def _worker(rank, world, port, q):
         ts._forward_and_loss_partials = fwd
         ts._loss_backward = lambda: None
         ts._capture_flags = capture
-        ts._norm_gated = lambda key=None: None
-        ts._commit_gated = commit
+        ts._norm = lambda key=None: None
+        ts._commit = commit
         ran = [ts.step() for _ in range(6)]
         ok = ran == [False, True] * 3 and decisions == [0, 1, 0]
         ok = ok and ts.gate[2].item() == 2 and ts.gate[3].item() == 1 and not ts.sync.pending
