@@ -193,6 +193,15 @@ __device__ __forceinline__ void store8_f32(float* base, int64_t elem_off, const 
   p[1] = make_float4(v[4], v[5], v[6], v[7]);
 }
 
+// splitmix64 finaliser: the hash of the counter-based generators (crd_dropout_masks, crd_augment_draw).  Element i of the draw
+// (seed, counter) is splitmix64(splitmix64(seed ^ counter * 0xD1342543DE82EF95) + i); its top 24 bits are the uniform.
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 // ---- order-independent sums (include/camradepth_hip.h: crd_sum_t) -------------------------------------------------------
 // A partial is rounded once to the fixed-point grid (the power-of-two scaling is exact in fp32) and added with a 64-bit
 // integer atomic; the total does not depend on the order of arrival.

@@ -530,12 +530,6 @@ __global__ __launch_bounds__(TPB) void k_wgrad_unpack(const crd_unpack_entry* ta
 
 // out[r][c] = u(r,c) < keep[r] ? 1/keep[r] : 0 with a counter-based hash RNG; *counter advances once per launch,
 // so a captured graph draws fresh masks on every replay.
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __global__ __launch_bounds__(TPB) void k_dropout_masks(float* out, const float* keep, int rows, int cols, unsigned long long seed,
                                                        unsigned long long* counter) {
   const unsigned long long epoch = *counter;

@@ -99,7 +99,7 @@ class DgnDesc(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 11         # include/camradepth_hip.h: CRD_ABI_VERSION
+ABI_VERSION = 12         # include/camradepth_hip.h: CRD_ABI_VERSION
 
 
 def load():
@@ -150,6 +150,8 @@ _SIGS = {
     "crd_slice_copy": "piipiiliip", "crd_f32_to_bf16_rows": "pipiiliplpiip", "crd_dropout_masks": "ppiiLpp", "crd_sigmoid_bwd": "pplp", "crd_head_conv2_fwd": "pppiiippiip", "crd_head_conv2_bwd": "ppiippiiippip", "crd_head_conv2_bwd_data": "ppiippiiipp", "crd_head_conv2_wgrad": "ppiipiiipip",
     "crd_weight_pack": "pilp", "crd_wgrad_unpack": "pilip",
     "crd_assemble_input": "pppiiifpp", "crd_gt_pyramid": "piiifppppp",
+    "crd_augment_draw": "ppiiiiifffffffiLLp", "crd_augment_lut": "piipp", "crd_augment_assemble": "pppppppiiiiifppppp",
+    "crd_augment_gather": "ppppiiiiiippppp", "crd_gt_pyramid_from_full": "piiipppp",
     "crd_resize_nearest_u8": "piiiipiip", "crd_resize_labels_nearest": "piiiipiip", "crd_seg_confusion": "ppiilppp",
     "crd_masked_l1_fwd": "pplpp", "crd_test_metrics": "ppilffpp", "crd_depth_eval": "ppilfffipp", "crd_masked_l1_bwd": "pplppfpp", "crd_ce_fwd": "ppiilpp",
     "crd_ce_focal_bwd": "ppiilppfpp",
@@ -170,6 +172,9 @@ SUM_DTYPE = torch.int64
 # crd_depth_eval: one scale per column of its [frames][bins][12] accumulator (CRD_EVAL_FRAC_BITS), at most CRD_EVAL_MAX_BINS bins
 EVAL_FRAC_BITS = (0, 32, 26, 24, 24, 36, 33, 31, 40, 0, 0, 0)
 EVAL_MAX_BINS = 64
+# crd_augment_draw: words per row of the table, the stream constant xor-ed into the seed, the bits of `enable`
+AUGMENT_WORDS, AUGMENT_STREAM = 8, 0xA0761D6478BD642F
+AUGMENT_GAMMA, AUGMENT_BRIGHTNESS, AUGMENT_COLOUR = 1, 2, 4
 
 
 def stat_value(t):

@@ -13,6 +13,7 @@ import torch
 
 from . import lib as L
 from . import losses as HL
+from .batch import augment_batch
 from .inference import InferenceGraph
 from .metrics import DepthEval, DepthMetrics, SegIoU
 from .optim import check_ema_decay, check_max_grad_norm
@@ -45,7 +46,7 @@ class Trainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, test_dataloader=None, learning_rate=6e-5, num_epochs=1,
                  update_interval=1, div_factor=2.0, max_depth=100.0, max_distances=(100.0, 50.0), num_classes=21, group=None,
                  use_graph=True, skip_nonfinite=False, criterion=None, max_grad_norm=None, ema_decay=None, ema_warmup=True,
-                 eval_with_ema=True):
+                 eval_with_ema=True, augment=None):
         ema_decay = check_ema_decay(ema_decay, "camradepth_amd.runner.Trainer")        # refused before anything is touched
         if model.flat is None or not model.flat.is_cuda:
             raise L.CrdError("camradepth_amd.runner.Trainer needs the model on an MI355X (no CPU fallback)")
@@ -64,6 +65,8 @@ class Trainer:
         # runner.py:149; criterion = another {"depth": ..., "seg": ...} of camradepth_amd.losses (TrainStep refuses what it cannot record)
         self.criterion = criterion if criterion is not None else {"depth": HL.MaskedSmoothL1Loss(), "seg": HL.MaskedFocalLoss()}
         depth_criterion_mode(self.criterion)
+        # camradepth_amd.batch.Augment: crop / flip every TRAINING batch on the device (augment_batch); eval() and test() never augment
+        self.augment = augment
         self.step = None                     # the TrainStep of the batch shape seen last
         self._steps, self._train_state = {}, None     # (B, H, W) -> TrainStep, all sharing one TrainState
         self._infer = {}                     # (B, H, W) -> InferenceGraph
@@ -99,6 +102,8 @@ class Trainer:
         depth, stage4, rmse, seg = [], [], [], []
         for i, batch in enumerate(self.train_dataloader):
             b = unpack_batch(batch, self.cfg.input_channels)
+            if self.augment is not None:
+                b = augment_batch(b, self.augment)              # the crop's shape: its TrainStep comes from the same per-shape cache
             ts = self._train_step_for(b)
             if i == 0:
                 ts.start_epoch()

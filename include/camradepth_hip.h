@@ -64,7 +64,7 @@ int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
 int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 11       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 12       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -594,6 +594,58 @@ int crd_resize_nearest_u8(const void* src, int32_t B, int32_t SH, int32_t SW, in
  * `rows` rows are used; int64 [B][DH][DW] labels out (the dtype runner.py:189-190 casts to). */
 int crd_resize_labels_nearest(const void* src_u8, int32_t B, int32_t SH, int32_t SW, int32_t rows, int64_t* dst, int32_t DH,
                               int32_t DW, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batch augmentation on the device: random crop, horizontal flip, photometric jitter of the image.  The reference trains
+ * without augmentation, so these entries are defined here ("Augmentation").
+ *
+ * params: int32 [B][CRD_AUGMENT_WORDS], one row per sample:
+ *   0 y0   1 x0   2 flip (0 / 1)      int32
+ *   3 gamma   4 brightness   5..7 colour gain of the stored channels 0..2      fp32 bit patterns
+ * Geometry: output pixel (y, x) of sample b reads source pixel (y0 + y, x0 + (flip ? w - 1 - x : x)) of every tensor.  The kernels
+ * clamp y0 into [0, H - h] and x0 into [0, W - w], so no table makes them read outside the frame.  A flipped sample gets radar
+ * channel 4 (u = (x - cx) / f, mirrored with the camera) written as v == 0 ? 0 : -v; channel 5 is untouched.
+ * (h, w) is the whole frame, or a crop whose sides are multiples of 32.
+ * ------------------------------------------------------------------------------------------- */
+#define CRD_AUGMENT_WORDS 8
+/* The augmentation stream: crd_augment_draw hashes with seed ^ CRD_AUGMENT_STREAM, so that equal user seeds for dropout and
+ * augmentation give unrelated draws.  Element i = b * 8 + k of the draw (seed, counter):
+ *   hash = splitmix64(splitmix64((seed ^ CRD_AUGMENT_STREAM) ^ counter * 0xD1342543DE82EF95) + i),  t = hash >> 40,  u = t * 2^-24
+ *   y0 = (t * (H - h + 1)) >> 24,  x0 = (t * (W - w + 1)) >> 24,  flip = u < p_flip,
+ *   gamma / brightness / colour = lo + u * (hi - lo), each product and sum rounded to fp32 on its own
+ * -- the generator of crd_dropout_masks.  The slots are fixed: a transform that is switched off (its bit in `enable` clear) writes
+ * 1.0 and leaves the other words as they are.  counter is a HOST integer (assembly runs outside the captured step). */
+#define CRD_AUGMENT_STREAM 0xA0761D6478BD642Full
+#define CRD_AUGMENT_GAMMA 1
+#define CRD_AUGMENT_BRIGHTNESS 2
+#define CRD_AUGMENT_COLOUR 4
+/* Writes params and, when lut != NULL, the table of crd_augment_lut for it. */
+int crd_augment_draw(int32_t* params, float* lut, int32_t B, int32_t H, int32_t W, int32_t h, int32_t w, float p_flip,
+                     float gamma_lo, float gamma_hi, float brightness_lo, float brightness_hi, float colour_lo, float colour_hi,
+                     int32_t enable, uint64_t seed, uint64_t counter, crd_stream_t stream);
+/* lut: fp32 [B][3][256], the normalised image value of byte v in stored channel c of sample b, all in fp32:
+ *   t = v / 255;  t = powf(t, gamma) (gamma enabled);  t *= brightness (enabled);  t *= colour[c] (enabled);  t = min(max(t, 0), 1);
+ *   lut = (t - mean[c]) / std[c]          with the constants of crd_assemble_input
+ * With nothing enabled this is crd_assemble_input's own expression. */
+int crd_augment_lut(const int32_t* params, int32_t B, int32_t enable, float* lut, crd_stream_t stream);
+/* crd_assemble_input + the full level of crd_gt_pyramid + the label gather in one launch, cropped and flipped by params, the image
+ * through lut.  seg_u8: uint8 labels [B][H][W] or NULL; final_seg: int64 [B][h][w]; inter_seg (optional): int64 [B][h/2][w/2],
+ * inter_seg[y][x] = final_seg[2y + 1][2x + 1] (skimage order 0 at a halving, crd_resize_labels_nearest).  out: fp32
+ * [B][7 or 6][h][w] (rad_vel NULL -> 6), gt_full: fp32 [B][h][w]. */
+int crd_augment_assemble(const void* img_u8, const float* radar, const float* rad_vel, const float* depth, const void* seg_u8,
+                         const int32_t* params, const float* lut, int32_t B, int32_t H, int32_t W, int32_t h, int32_t w,
+                         float max_depth, float* out, float* gt_full, int64_t* final_seg, int64_t* inter_seg,
+                         crd_stream_t stream);
+/* The geometry alone, for tensors that are assembled already: image fp32 [B][C][H][W] -> [B][C][h][w] (channel 4 negated on flipped
+ * samples when C >= 6), gt_full fp32 [B][H][W] -> [B][h][w], seg int64 [B][H][W] or NULL -> seg_out [B][h][w] and (optional)
+ * inter_out [B][h/2][w/2]. */
+int crd_augment_gather(const float* image, const float* gt_full, const int64_t* seg, const int32_t* params, int32_t B, int32_t C,
+                       int32_t H, int32_t W, int32_t h, int32_t w, float* image_out, float* gt_out, int64_t* seg_out,
+                       int64_t* inter_out, crd_stream_t stream);
+/* The min-pool levels of crd_gt_pyramid from a full map that is inverse-normalised already (an augmented one: the levels are rebuilt
+ * from it, never cropped or flipped themselves -- with an even width the 3x3 / stride 2 / pad 1 windows are not mirror-symmetric). */
+int crd_gt_pyramid_from_full(const float* full, int32_t B, int32_t H, int32_t W, float* half, float* quarter, float* eighth,
+                             crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Losses (src/utils/loss_funcs.py:14-46,77-91; combination src/main/runner.py:197-218).
