@@ -107,23 +107,28 @@ __global__ __launch_bounds__(TPB) void k_masked_l1_bwd(const float* pred, const 
   }
 }
 
-// Cross entropy over NCHW fp32 logits, labels int64 [B][HW], ignore_index 255 (loss_funcs.py:22,27)
+// Cross entropy over NCHW fp32 logits, labels int64 [B][HW], ignore_index 255 (loss_funcs.py:22,27).  Any other label outside
+// [0, C) -- torch raises on it -- never forms an address: the pixel adds nothing to the sum or the count and is counted in acc[2]
+// (as k_seg_confusion counts it in oor[f]); the callers raise on a non-zero count.
 __global__ __launch_bounds__(TPB) void k_ce_fwd(const float* logits, const long long* labels, int C, long long HW, long long rows,
                                                 crd_sum_t* acc) {
-  float s = 0.f, cnt = 0.f;
+  float s = 0.f, cnt = 0.f, bad = 0.f;
   for (long long r = (long long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long long)gridDim.x * TPB) {
     const long long lab = labels[r];
     if (lab == 255) continue;
+    if (lab < 0 || lab >= C) { bad += 1.f; continue; }
     const long long b = r / HW, p = r - b * HW;
     const float* base = logits + (b * C) * HW + p;
     float mx = -INFINITY;
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, base[(long long)c * HW]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(base[(long long)c * HW] - mx);
-    s += mx + logf(se) - base[lab * HW];
+    // log-sum-exp minus the SHIFTED target logit: (mx + log se) - x[lab] would round at the magnitude of the logits themselves
+    // (5e-4 per pixel for logits near 1e4), x[lab] - mx is small and nearly exact
+    s += logf(se) - (base[lab * HW] - mx);
     cnt += 1.f;
   }
-  block_atomic3(s, cnt, 0.f, acc);
+  block_atomic3(s, cnt, bad, acc);
 }
 
 // focal on the scalar mean CE: F=(1-e^-ce)^2 ce ; dF/dce = 2(1-pt)pt ce + (1-pt)^2
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(TPB) void k_ce_focal_bwd(const float* logits, const
     const long long b = r / HW, p = r - b * HW;
     const float* base = logits + (b * C) * HW + p;
     float* dbase = dlogits + (b * C) * HW + p;
-    if (lab == 255) {
+    if (lab == 255 || lab < 0 || lab >= C) {      // ignored, or out of range (counted by k_ce_fwd): no gradient
       for (int c = 0; c < C; ++c) dbase[(long long)c * HW] = 0.f;
       continue;
     }

@@ -179,6 +179,10 @@ class _Focal(torch.autograd.Function):
         _allreduce_acc(acc)
         ctx.save_for_backward(lg, tg, acc)
         a = L.stat_checked(acc)
+        n_bad = int(acc[2]) >> L.STAT_FRAC_BITS      # (the sums are on their way to the host already: no further wait)
+        if n_bad:
+            raise L.CrdError(f"MaskedFocalLoss: {n_bad} target label(s) are neither in [0, {Cc}) nor ignore_index 255 "
+                             "(torch.nn.functional.cross_entropy raises on them)")
         ce = (a[0] / a[1]).float()
         pt = torch.exp(-ce)
         return (1 - pt) ** 2 * ce
@@ -253,7 +257,8 @@ class SmoothnessLoss(nn.Module):
 
 class MaskedFocalLoss(nn.Module):
     """Focal transform (gamma=2) of the scalar mean cross entropy, ignore_index=255
-    (reference: src/utils/loss_funcs.py:14-34)."""
+    (reference: src/utils/loss_funcs.py:14-34).  A target label that is neither 255 nor a class raises CrdError naming how many
+    there are (torch raises there too); the kernels never read through such a label."""
 
     def __init__(self, weight=None, gamma=2, reduction="mean"):
         super().__init__()

@@ -263,7 +263,7 @@ class TrainStep:
         self.gt = {"full": torch.zeros((B, 1, H, W), device=self.dev), "half": torch.zeros((B, 1, H // 2, W // 2), device=self.dev),
                    "quarter": torch.zeros((B, 1, H // 4, W // 4), device=self.dev),
                    "seg": torch.zeros((B, H, W), dtype=torch.int64, device=self.dev)}
-        self.acc = torch.zeros(16, dtype=L.SUM_DTYPE, device=self.dev)     # crd_sum_t: 4 x (sum, count, sum sq, -) for full/half/quarter/ce
+        self.acc = torch.zeros(16, dtype=L.SUM_DTYPE, device=self.dev)     # crd_sum_t: 4 x (sum, count, sum sq, -) for full/half/quarter/ce (ce: sum, count, #labels out of range, -)
         if self._depth_mode == "berhu":
             self.maxbits = torch.zeros(4, dtype=torch.int32, device=self.dev)     # per level: fp32 bits of max |d| (MAX-reduced)
             self.berhu_acc = torch.zeros(8, dtype=L.SUM_DTYPE, device=self.dev)   # per level: (sum part1, sum part2 numerators)
@@ -746,9 +746,14 @@ class TrainStep:
 
     def losses(self):
         """Host view of the last iteration's loss terms (synchronises): the criterion's value per depth level; "rmse" is
-        sqrt(sum d^2 / count) of the full level whatever the criterion."""
+        sqrt(sum d^2 / count) of the full level whatever the criterion.  Raises CrdError when the iteration's segmentation target
+        held a label that is neither a class nor ignore_index 255 (crd_ce_fwd counts them in its acc[2]; torch raises there)."""
         a = L.stat_value(self.acc.cpu())
-        if L.nonfinite():
+        dropped = L.nonfinite()
+        if self.sup and a[14] != 0:
+            raise L.CrdError(f"TrainStep: {int(a[14])} segmentation label(s) of the last iteration are neither in "
+                             f"[0, {self.model.cfg.num_classes}) nor ignore_index 255")
+        if dropped:
             # a NaN / infinite / out-of-range partial was dropped from a fixed-point sum since the last check (include/camradepth_hip.h:
             # crd_nonfinite_status): the sums are not what the reference would have computed -- it reports NaN here, so do we
             nan = float("nan")

@@ -714,10 +714,14 @@ int crd_depth_eval(const float* pred, const float* gt, int32_t frames, int64_t n
 int crd_masked_l1_bwd(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const float* gout,
                       float gmul, float* dpred, crd_stream_t stream);
 /* NCHW fp32 logits [B][C][HW], int64 labels [B][HW], ignore_index 255:
- * acc[0] += sum -log softmax[label], acc[1] += #valid */
+ * acc[0] += sum -log softmax[label], acc[1] += #valid, acc[2] += #out-of-range (all three crd_sum_t, CRD_STAT_FRAC_BITS).
+ * A label that is neither 255 nor in [0, C) is OUT OF RANGE (torch raises on it): it is never used to form an address, adds
+ * nothing to acc[0] and acc[1], gets a zero gradient from crd_ce_focal_bwd, and is counted in acc[2] -- the caller decides;
+ * MaskedFocalLoss and TrainStep.losses() raise on a non-zero count.  The call owns acc[0..2]. */
 int crd_ce_fwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, crd_sum_t* acc,
                crd_stream_t stream);
-/* focal on the scalar mean CE (loss_funcs.py:27-29): dlogits = gmul*gout[0]*dF/dce*(softmax-onehot)/acc[1] */
+/* focal on the scalar mean CE (loss_funcs.py:27-29): dlogits = gmul*gout[0]*dF/dce*(softmax-onehot)/acc[1] on the valid pixels,
+ * 0 on ignored and out-of-range ones (gout may be NULL = 1) */
 int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, const crd_sum_t* acc,
                      const float* gout, float gmul, float* dlogits, crd_stream_t stream);
 
