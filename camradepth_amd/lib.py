@@ -99,7 +99,7 @@ class DgnDesc(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 12         # include/camradepth_hip.h: CRD_ABI_VERSION
+ABI_VERSION = 13         # include/camradepth_hip.h: CRD_ABI_VERSION
 
 
 def load():
@@ -152,6 +152,7 @@ _SIGS = {
     "crd_assemble_input": "pppiiifpp", "crd_gt_pyramid": "piiifppppp",
     "crd_augment_draw": "ppiiiiifffffffiLLp", "crd_augment_lut": "piipp", "crd_augment_assemble": "pppppppiiiiifppppp",
     "crd_augment_gather": "ppppiiiiiippppp", "crd_gt_pyramid_from_full": "piiipppp",
+    "crd_radar_project": "pppiipppipiiiffpppppppp", "crd_radar_rasterize": "ppppppppiipiiiiiplppp",
     "crd_resize_nearest_u8": "piiiipiip", "crd_resize_labels_nearest": "piiiipiip", "crd_seg_confusion": "ppiilppp",
     "crd_masked_l1_fwd": "pplpp", "crd_test_metrics": "ppilffpp", "crd_depth_eval": "ppilfffipp", "crd_masked_l1_bwd": "pplppfpp", "crd_ce_fwd": "ppiilpp",
     "crd_ce_focal_bwd": "ppiilppfpp",

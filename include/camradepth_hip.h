@@ -64,7 +64,7 @@ int crd_nonfinite_status(int32_t reset, crd_stream_t stream);
 int crd_nonfinite_capture(int32_t* window_flag, crd_stream_t stream);
 
 const char* crd_last_error(void);
-#define CRD_ABI_VERSION 12       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
+#define CRD_ABI_VERSION 13       /* bumped whenever a struct layout or signature changes: the binding refuses a stale library */
 int crd_version(void);          /* CRD_ABI_VERSION of the library that was built */
 const char* crd_arch(void);     /* "gfx950" */
 
@@ -646,6 +646,48 @@ int crd_augment_gather(const float* image, const float* gt_full, const int64_t* 
  * from it, never cropped or flipped themselves -- with an even width the 3x3 / stride 2 / pad 1 windows are not mirror-symmetric). */
 int crd_gt_pyramid_from_full(const float* full, int32_t B, int32_t H, int32_t W, float* half, float* quarter, float* eighth,
                              crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Radar front end: accumulated radar sweeps -> the radar [B][H][W][3] and rad_vel [B][H][W] maps of crd_assemble_input.  The
+ * reference makes them offline (lib/fuse_radar.py, driven by scripts/cal_radar.py and scripts/show_v_comp.py); a live pipeline
+ * needs them per frame ("Radar front end").  All arithmetic is fp64.  Every fp64 quantity is passed through device
+ * memory.  Neither entry allocates or synchronises; both may be captured in a graph.
+ *
+ * Points of all frames lie in one array; frame b owns the points frame_offsets[b] .. frame_offsets[b + 1] - 1 (int32 [B + 1] on the
+ * device, non-decreasing; an empty frame repeats a value).  A point outside every range is invalid (project) / skipped (rasterize),
+ * so a captured call sized for n_points can be replayed with fewer.  K: row-major 3x3 intrinsics, one matrix for all frames
+ * (k_stride 0) or one per frame (k_stride 9); fx = K[0], cx = K[2], fy = K[4], cy = K[5].
+ * ------------------------------------------------------------------------------------------- */
+/* The projection nested in merge_selected_radar (fuse_radar.py:30-74, :144-151).  points: fp64 [n_points][5] = x, y, z, vx_comp,
+ * vy_comp in the radar sensor frame; sweep_index: int32 [n_points], the row of the point's sweep in the per-sweep tables
+ * cam1_from_sensor / cam2_from_sensor (fp64 [n_sweeps][3][4], the pose chain sensor -> car -> global -> car -> camera multiplied by
+ * the caller) and lags (fp64 [n_sweeps][2]: camera time minus sweep time in seconds for camera 1 and 2, signed).  Per camera c:
+ *   xs = x + vx_comp * lag_c,  ys = y + vy_comp * lag_c,  (X, Y, Z) = M_c . (xs, ys, z, 1),
+ *   px_c = (fx * X + cx * Z) / Z,  py_c = (fy * Y + cy * Z) / Z
+ * valid = not (|x| < min_distance and |y| < min_distance) and, for both cameras, Z_c >= min_z, 0 < px_c < im_w, 0 < py_c < im_h;
+ * a NaN, a sweep_index outside the tables or a point outside every frame gives valid = 0.  Outputs, over all points in their order
+ * (nothing is compacted: the rasteriser's tie rule is by index): x1, y1, depth1 = Z_1, x2, y2, v_comp = sqrt(vx_comp^2 + vy_comp^2). */
+int crd_radar_project(const double* points, const int32_t* sweep_index, const int32_t* frame_offsets, int32_t B, int32_t n_points,
+                      const double* cam1_from_sensor, const double* cam2_from_sensor, const double* lags, int32_t n_sweeps,
+                      const double* K, int32_t k_stride, int32_t im_h, int32_t im_w, float min_distance, float min_z, double* x1,
+                      double* y1, double* depth1, double* x2, double* y2, double* v_comp, uint8_t* valid, crd_stream_t stream);
+/* cal_depthMap_flow (:156-204) + radarFlow2uv (:276-303).  h_new = im_h / s, w_new = im_w / s (integer division, s =
+ * downsample_scale).  Per point with valid != 0 (valid NULL: every point): xa = clip((x1 + 0.5) / s - 0.5, 0, w_new - 1), ya, xb, yb
+ * alike from y1, x2, y2; its pixel is (rint(ya), rint(xa)), half to even.  A pixel goes to its point of smallest depth1 (compared as
+ * fp64), the lowest index among equal depths -- what the reference's loop leaves -- independent of the order of arrival.  Rows above
+ * y_cutoff are dropped: output row r is map row r + y_cutoff.  At the winner i of output pixel (r, c):
+ *   radar[b][r][c] = (depth1[i], u, v),  rad_vel[b][r][c] = v_comp[i] > 0.5
+ *   xm = fp32(c + (xb - xa)),  ym = fp32(r + (yb - ya))          (one rounding of the fp64 sum)
+ *   u = (xm - cx / s) / (fx / s),  v = (ym - (cy / s - y_cutoff)) / (fx / s)          (fx in both, as the reference)
+ * rounded to fp32; every other pixel is 0.  A point with a non-finite x1, y1, depth1, x2, y2 or v_comp, or depth1 <= 0, is skipped
+ * (the reference raises on NaN coordinates and treats a zero depth as an empty pixel).  The time and RCS maps are not produced.
+ * radar: fp32 [B][h_new - y_cutoff][w_new][3], rad_vel: fp32 [B][h_new - y_cutoff][w_new], both written in full.  workspace: n_pix =
+ * B * (h_new - y_cutoff) * w_new winners (uint32) and, from the next multiple of 16 bytes, n_pix depth keys (uint64);
+ * workspace_bytes >= ((4 * n_pix + 15) & ~15) + 8 * n_pix.  workspace, radar and rad_vel are 16-byte aligned. */
+int crd_radar_rasterize(const double* x1, const double* y1, const double* depth1, const double* x2, const double* y2,
+                        const double* v_comp, const uint8_t* valid, const int32_t* frame_offsets, int32_t B, int32_t n_points,
+                        const double* K, int32_t k_stride, int32_t im_h, int32_t im_w, int32_t downsample_scale, int32_t y_cutoff,
+                        void* workspace, int64_t workspace_bytes, float* radar, float* rad_vel, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Losses (src/utils/loss_funcs.py:14-46,77-91; combination src/main/runner.py:197-218).
