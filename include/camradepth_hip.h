@@ -690,6 +690,70 @@ int crd_radar_rasterize(const double* x1, const double* y1, const double* depth1
                         void* workspace, int64_t workspace_bytes, float* radar, float* rad_vel, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Lidar ground-truth front end: accumulated lidar sweeps -> the gt_depth [B][H][W] map of crd_gt_pyramid / crd_augment_assemble, with
+ * the flow (u, v) and low-height mask the reference stores beside it.  The reference makes them offline (lib/fuse_lidar.py, driven by
+ * scripts/cal_gt.py) in a Python loop over about a million points per key frame ("Lidar ground-truth front end").
+ * The conventions are the radar front end's: fp64 arithmetic, fp64 quantities through device memory or as IEEE-754 bit patterns
+ * (uint64_t ..._f64_bits), frame_offsets, K / k_stride, no allocation, no synchronisation, capturable in a graph on one stream.  The
+ * two entries add no struct and change no signature: CRD_ABI_VERSION stays.
+ * ------------------------------------------------------------------------------------------- */
+/* current_to_global_at_ref_time + proj2im (fuse_lidar.py:84-179), the pose chains multiplied by the caller.  points: fp64
+ * [n_points][3] in the lidar sensor frame; sweep_index: int32 [n_points], the row s of the point's sweep in
+ *   cam1_from_sensor, cam2_from_sensor  fp64 [n_sweeps][3][4]   sensor -> car -> global -> car -> camera 1 / 2
+ *   car_z_from_sensor                   fp64 [n_sweeps][4]      the z row of car-from-sensor (the height mask)
+ *   sweep_boxes                         int32 [n_sweeps + 1]    sweep s owns the box entries sweep_boxes[s] .. sweep_boxes[s + 1] - 1
+ * A box entry e is a box that exists at the sweep's time and at the camera times, in the reference's iteration order (:118-119):
+ *   box_entries[e]  fp64 [15] = box_from_sensor [3][4] (the box frame at the sweep's time), then the half extents l/2, w/2, h/2
+ *   box_id[e]       int32, the row k of the box in cam1_from_box / cam2_from_box (fp64 [n_boxes][3][4]: camera c from the box's pose
+ *                   at camera c's time) and vehicle (uint8 [n_boxes], non-zero: 'vehicle' is in the category name, :153)
+ * Per point p = (x, y, z) of sweep s:
+ *   z_car = car_z . (x, y, z, 1);  low_h = h_min <= z_car <= h_max                                        (:47-56, :109)
+ *   q_e = box_from_sensor_e . (x, y, z, 1);  the point belongs to the FIRST entry e of its sweep with |q_e.x| < l/2, |q_e.y| < w/2,
+ *   |q_e.z| < h/2, all six strict (:132-137) -- the reference takes a box's points out of the pool before it tests the next box
+ *   (X, Y, Z)_c = cam_c_from_box[k] . (q_e, 1) for a box point, cam_c_from_sensor[s] . (x, y, z, 1) for any other
+ *   px_c = (fx * X + cx * Z) / Z,  py_c = (fy * Y + cy * Z) / Z;  in_box = the point is in a box and vehicle[k]
+ *   valid = not (|x| < min_distance and |y| < min_distance) and, for both cameras, Z_c >= min_z, 0 < px_c < im_w, 0 < py_c < im_h
+ * A NaN fails every test.  A point outside every frame, with a sweep_index outside the tables or in an entry whose box_id is outside
+ * [0, n_boxes) gives zeros, valid = low_h = in_box = 0 and box_entry = -1, and none of its tables is read.  Outputs over all points in
+ * their order (nothing is compacted: the tie rule of crd_lidar_ground_truth is by index): x1, y1, depth1 = Z_1, x2, y2 (fp64), low_h,
+ * in_box, valid (uint8), box_entry (int32: the entry e the point belongs to, or -1).
+ * Not the reference's: it keeps points as float32 and rounds after every transform (the devkit's LidarPointCloud), here the chain
+ * stays fp64; it moves box points behind the others (:157), here the order is the input's (it only decides exact fp64 depth ties). */
+int crd_lidar_project(const double* points, const int32_t* sweep_index, const int32_t* frame_offsets, int32_t B, int32_t n_points,
+                      const double* cam1_from_sensor, const double* cam2_from_sensor, const double* car_z_from_sensor,
+                      const int32_t* sweep_boxes, int32_t n_sweeps, const double* box_entries, const int32_t* box_id, int32_t n_entries,
+                      const double* cam1_from_box, const double* cam2_from_box, const uint8_t* vehicle, int32_t n_boxes,
+                      const double* K, int32_t k_stride, int32_t im_h, int32_t im_w, float min_distance, float min_z,
+                      uint64_t h_min_f64_bits, uint64_t h_max_f64_bits, double* x1, double* y1, double* depth1, double* x2, double* y2,
+                      uint8_t* low_h, uint8_t* in_box, uint8_t* valid, int32_t* box_entry, crd_stream_t stream);
+/* cal_depthMap_flow (:281-323), filter_occlusion_by_bbox (:634-676), filter_occlusion (:554-568) and lidarFlow2uv (:571-598), in the
+ * order scripts/cal_gt.py:125-132 applies them.  h_new = im_h / s, w_new = im_w / s, h = h_new - y_cutoff, w = w_new.
+ * Rasterise: crd_radar_rasterize's rule.  Per point with valid != 0 (valid NULL: every point): xa = clip((x1 + 0.5) / s - 0.5, 0,
+ * w_new - 1), ya, xb, yb alike; its pixel is (rint(ya) - y_cutoff, rint(xa)), half to even, rows above the cutoff dropped.  A pixel
+ * goes to its point of smallest depth1 (fp64), the lowest index among equal depths.  A point with a non-finite x1, y1, depth1, x2 or y2,
+ * or depth1 <= 0, is skipped.
+ * Box filter, on when seg != NULL (seg: uint8 [B][h][w], non-zero = vehicle; corners: fp64 [n_boxes][8][4] = x, y, depth, in_view
+ * (non-zero) of the eight projected corners of a box; corner_offsets: int32 [B + 1], frame b owns the boxes corner_offsets[b] ..
+ * corner_offsets[b + 1] - 1).  Per box: xs = clip((x + 0.5) / s - 0.5, 0, w - 1) and ys = clip((y + 0.5) / s - 0.5 - y_cutoff, 0,
+ * h - 1) over its IN-VIEW corners give the rectangle rint(min xs) .. rint(max xs), rint(min ys) .. rint(max ys); d_max is the largest
+ * depth of ALL eight.  The winner i of pixel (r, c) is dropped when seg[b][r][c] != 0, in_box[i] == 0 and some box of frame b has
+ * (r, c) in its rectangle and depth1[i] > d_max.  A box with no corner in view (or a non-finite in-view coordinate) does nothing.
+ * Flow filter, on when flow_im != NULL (fp32 [B][h][w][2]): at a pixel that is left, e = (xb - xa, yb - ya) - flow_im[b][r][c]
+ * in fp64; the pixel is dropped when sqrt(ex * ex + ey * ey) > thres (thres_f64_bits: a double as its bit pattern).
+ * At a pixel that is left:  gt[b][r][c] = (depth1[i], u, v) with u, v as crd_radar_rasterize's; depth[b][r][c] = depth1[i];
+ * msk_lh[b][r][c] = low_h[i].  Every other pixel is 0 in all three.  gt: fp32 [B][h][w][3], depth: fp32 [B][h][w], msk_lh: uint8
+ * [B][h][w], all written in full.  workspace, with n_pix = B * h * w: n_pix winners (uint32); from the next multiple of 16 bytes n_pix
+ * depth keys (uint64); from the next multiple of 16 bytes, with seg only, 32 bytes per box; so workspace_bytes >=
+ * ((((4 * n_pix + 15) & ~15) + 8 * n_pix + 15) & ~15) + (seg ? 32 * n_boxes : 0).  workspace, gt and depth are 16-byte aligned, msk_lh
+ * 4-byte aligned.  Launches: clear, [boxes], min depth, min index, resolve. */
+int crd_lidar_ground_truth(const double* x1, const double* y1, const double* depth1, const double* x2, const double* y2,
+                           const uint8_t* low_h, const uint8_t* in_box, const uint8_t* valid, const int32_t* frame_offsets, int32_t B,
+                           int32_t n_points, const double* K, int32_t k_stride, int32_t im_h, int32_t im_w, int32_t downsample_scale,
+                           int32_t y_cutoff, const uint8_t* seg, const double* corners, const int32_t* corner_offsets, int32_t n_boxes,
+                           const float* flow_im, uint64_t thres_f64_bits, void* workspace, int64_t workspace_bytes, float* gt,
+                           float* depth, uint8_t* msk_lh, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Losses (src/utils/loss_funcs.py:14-46,77-91; combination src/main/runner.py:197-218).
  * ------------------------------------------------------------------------------------------- */
 /* acc[0] += sum smooth_l1(pred-target), acc[1] += #(target>0), acc[2] += sum (target-pred)^2 ; crd_sum_t with
