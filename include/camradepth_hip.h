@@ -754,6 +754,58 @@ int crd_lidar_ground_truth(const double* x1, const double* y1, const double* dep
                            float* depth, uint8_t* msk_lh, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Point-cloud back end: a depth map -> 3-D points in metres in the caller's frame ("Point-cloud back end").  The
+ * inverse of the two rasterisers above and their conventions: fp64 arithmetic, fp64 quantities through device memory or as IEEE-754
+ * bit patterns (uint64_t ..._f64_bits), K / k_stride, h_new = im_h / s, w_new = im_w / s, h = h_new - y_cutoff, w = w_new, no
+ * allocation, no synchronisation, capturable in a graph on one stream, arguments checked before any GPU call.  The two entries add no
+ * struct and change no signature: CRD_ABI_VERSION stays.
+ *
+ * Both read pixel (r, c) of frame b as p = (double)depth[b][r][c] (depth: fp32 [B][h][w]) and compute, every operation rounded on its
+ * own (nothing is contracted into a fused multiply-add), with s = downsample_scale:
+ *   1. d = max_depth * (1.0 - p)        encoding 0: normalised inverse depth, the network's output and gt_full (dataloader.py:245)
+ *      d = p                            encoding 1: metres, the depth of crd_lidar_ground_truth, channel 0 of crd_radar_rasterize
+ *   2. xf = (c + 0.5) * s - 0.5,  yf = (r + y_cutoff + 0.5) * s - 0.5      the full-resolution coordinate the rasterisers scale and
+ *                                                                          round to this pixel: xa = (x + 0.5) / s - 0.5
+ *   3. X = ((xf - cx) / fx) * d,  Y = ((yf - cy) / fy) * d,  Z = d         d is z-depth; fy for Y (the rasterisers' "fx for v" is the
+ *                                                                          flow channels' alone)
+ *   4. o_i = ((T[i][0] * X + T[i][1] * Y) + T[i][2] * Z) + T[i][3]         T = out_from_cam: fp64 [3][4] row-major, one for all frames
+ *      (t_stride 0) or one per frame (t_stride 12), the pose chain multiplied by the caller; NULL: o = (X, Y, Z)
+ *   5. each o_i is rounded to fp32 once.
+ * The pixel is valid when p is finite, d > 0, min_range <= d <= max_range, for encoding 0 not (skip_empty and p == 0), for encoding 1
+ * p > 0, mask == NULL or mask[b][r][c] != 0 (uint8 [B][h][w]), and labels == NULL or keep[labels[b][r][c]] != 0 (labels: uint8
+ * [B][h][w]; keep: uint8 [256] on the device; labels needs keep).  p = 0 in a target map is "no ground truth" (skip_empty = 1); in a
+ * prediction it is max_depth metres (skip_empty = 0).  max_depth is finite and positive, min_range and max_range are not NaN.  depth
+ * is 16-byte aligned, mask and labels 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+/* The organised cloud, one launch: points fp32 [B][h][w][3] and valid uint8 [B][h][w], both written in full; an invalid pixel gets
+ * (0, 0, 0) and 0.  points is 16-byte aligned, valid 4-byte aligned. */
+int crd_depth_unproject(const float* depth, int32_t B, int32_t im_h, int32_t im_w, int32_t downsample_scale, int32_t y_cutoff,
+                        const double* K, int32_t k_stride, const double* out_from_cam, int32_t t_stride, int32_t encoding,
+                        uint64_t max_depth_f64_bits, uint64_t min_range_f64_bits, uint64_t max_range_f64_bits, int32_t skip_empty,
+                        const uint8_t* mask, const uint8_t* labels, const uint8_t* keep, float* points, uint8_t* valid,
+                        crd_stream_t stream);
+/* The compact cloud.  The candidates are the pixels with r % stride == 0 and c % stride == 0 (stride >= 1): n_cand = ceil(h / stride) *
+ * ceil(w / stride) per frame, cap = B * n_cand in all.  The valid candidates are written densely, ordered by (b, r, c) ascending:
+ *   xyz            fp32 [cap][3]
+ *   rgb            uint8 [cap][3] or NULL, gathered from image (uint8 [B][h][w][3], the layout of crd_assemble_input; rgb needs image)
+ *   label          uint8 [cap] or NULL, the point's labels value (label needs labels)
+ *   pixel          int32 [cap] or NULL, r * w + c
+ *   frame_offsets  int32 [B + 1], WRITTEN here: frame b owns the rows frame_offsets[b] .. frame_offsets[b + 1] - 1, frame_offsets[B] is
+ *                  the number of points -- the layout crd_radar_project and crd_lidar_project take.
+ * Rows from frame_offsets[B] on are left untouched.  The order is a function of the inputs alone and the same bits every run: no atomic
+ * and no workgroup waiting on another.  Three launches: the valid candidates of every tile of CRD_CLOUD_TILE consecutive candidates
+ * of one frame (wave ballots), the exclusive prefix sums of the tile counts and frame_offsets (one workgroup), the scatter (the rank
+ * inside a tile from the ballots).  workspace: one int32 per tile, 4-byte aligned:
+ *   workspace_bytes >= 4 * B * ceil(n_cand / CRD_CLOUD_TILE). */
+#define CRD_CLOUD_TILE 1024
+int crd_point_cloud(const float* depth, int32_t B, int32_t im_h, int32_t im_w, int32_t downsample_scale, int32_t y_cutoff,
+                    const double* K, int32_t k_stride, const double* out_from_cam, int32_t t_stride, int32_t encoding,
+                    uint64_t max_depth_f64_bits, uint64_t min_range_f64_bits, uint64_t max_range_f64_bits, int32_t skip_empty,
+                    const uint8_t* mask, const uint8_t* labels, const uint8_t* keep, int32_t stride, const uint8_t* image,
+                    void* workspace, int64_t workspace_bytes, float* xyz, uint8_t* rgb, uint8_t* label, int32_t* pixel,
+                    int32_t* frame_offsets, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Losses (src/utils/loss_funcs.py:14-46,77-91; combination src/main/runner.py:197-218).
  * ------------------------------------------------------------------------------------------- */
 /* acc[0] += sum smooth_l1(pred-target), acc[1] += #(target>0), acc[2] += sum (target-pred)^2 ; crd_sum_t with
