@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import lib as L
-from .radar import _dev, _intrinsics, _size, map_shape
+from ._frontend import _dev, _intrinsics, _size, map_shape
 
 TILE = 1024              # include/camradepth_hip.h: CRD_CLOUD_TILE, candidates per workgroup of the compact path
 ENCODINGS = {"inverse": 0, "metres": 1}

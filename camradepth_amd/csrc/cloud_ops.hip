@@ -3,7 +3,7 @@
 // cutoff and the frame_offsets layout are theirs.  crd_depth_unproject writes the organised cloud in one launch; crd_point_cloud writes
 // the valid candidates densely in (b, r, c) order with three launches (count per tile, scan of the tile counts, scatter), no workgroup
 // waiting on another and no atomic.  All arithmetic is fp64; each coordinate is rounded to fp32 once.
-#include "common.h"
+#include "raster.h"       // the pixel-centre convention (to_full inverts the rasterisers' to_small) and the quad store of a [.][3] map
 #include <string.h>
 
 // the results are specified operation by operation (include/camradepth_hip.h) and compared bit for bit with NumPy, which never fuses
@@ -37,8 +37,8 @@ __device__ __forceinline__ bool metres(const Cloud& a, float pf, double& d) {
 // Steps 2 to 5 for pixel (r, c) at depth d: Kb the frame's intrinsics, Tb its out_from_cam or NULL.
 __device__ __forceinline__ void point_of(const Cloud& a, const double* Kb, const double* Tb, int r, int c, double d, float& x, float& y,
                                          float& z) {
-  const double xf = ((double)c + 0.5) * a.s - 0.5;
-  const double yf = ((double)(r + a.y_cutoff) + 0.5) * a.s - 0.5;
+  const double xf = to_full((double)c, a.s);
+  const double yf = to_full((double)(r + a.y_cutoff), a.s);
   const double X = ((xf - Kb[2]) / Kb[0]) * d, Y = ((yf - Kb[5]) / Kb[4]) * d, Z = d;
   if (Tb) {
     x = (float)(((Tb[0] * X + Tb[1] * Y) + Tb[2] * Z) + Tb[3]);
@@ -93,10 +93,7 @@ __global__ __launch_bounds__(TPB) void k_cloud_unproject(Cloud a, long long n_pi
       }
     }
     if (whole) {
-      float4* dst = reinterpret_cast<float4*>(points + p0 * 3);
-      dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-      dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-      dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+      store_quad3(points, p0, o);
       *reinterpret_cast<unsigned*>(valid + p0) = ok4;
     } else {
       for (int k = 0; k < n; ++k) {
@@ -311,9 +308,9 @@ extern "C" int crd_depth_unproject(const float* depth, int32_t B, int32_t im_h, 
   CRD_CHECK_ARG(points && valid, "crd_depth_unproject: null pointer (points, valid)");
   CRD_CHECK_ARG(aligned(points, 16) && aligned(valid, 4),
                 "crd_depth_unproject: bad argument (points must be 16-byte aligned, valid 4-byte aligned)");
-  const long long n_pix = (long long)B * a.h * a.w, blocks = ((n_pix + 3) / 4 + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_cloud_unproject, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(TPB), 0, as_stream(stream), a, n_pix, points,
-                     valid);
+  const long long n_pix = (long long)B * a.h * a.w;
+  static_assert(TPB == ZBUF_TPB, "quad_blocks counts blocks of ZBUF_TPB threads");
+  hipLaunchKernelGGL(k_cloud_unproject, dim3(quad_blocks(n_pix)), dim3(TPB), 0, as_stream(stream), a, n_pix, points, valid);
   CRD_LAUNCH_CHECK("crd_depth_unproject");
   return CRD_OK;
 }

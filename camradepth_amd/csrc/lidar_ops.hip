@@ -4,7 +4,7 @@
 // cal_depthMap_flow (:281-323), filter_occlusion_by_bbox (:634-676), filter_occlusion (:554-568) and lidarFlow2uv (:571-598).  All
 // arithmetic is fp64, as NumPy's.  A key frame is about a million points on a third of a million pixels: the two atomic passes of the
 // rasteriser are the hot path.
-#include "common.h"
+#include "raster.h"       // the projection arithmetic, the z-buffer passes and the helpers of the resolve pass are shared with radar_ops.hip
 #include <string.h>
 
 // the ground-truth stage is pinned bit for bit to NumPy, which never fuses a multiply into an add
@@ -12,28 +12,8 @@
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr unsigned NO_POINT = 0xffffffffu;
+constexpr int TPB = ZBUF_TPB;
 constexpr int ENTRY = 15;                      // doubles per box entry: box_from_sensor [3][4], then l/2, w/2, h/2
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < INFINITY; }      // false for NaN as well
-
-// The frame of point p: the b with off[b] <= p < off[b + 1], or -1.  off has B + 1 non-decreasing entries (empty frames repeat a value).
-__device__ __forceinline__ int frame_of(const int32_t* off, int B, int p) {
-  int lo = 0, hi = B + 1;                      // first j in [0, B + 1] with off[j] > p
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] > p) hi = mid; else lo = mid + 1;
-  }
-  return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
-
-// M . (x, y, z, 1) for a row-major 3 x 4 matrix
-__device__ __forceinline__ void rigid(const double* M, double x, double y, double z, double& X, double& Y, double& Z) {
-  X = M[0] * x + M[1] * y + M[2] * z + M[3];
-  Y = M[4] * x + M[5] * y + M[6] * z + M[7];
-  Z = M[8] * x + M[9] * y + M[10] * z + M[11];
-}
 
 struct Project {
   const double* pts;
@@ -112,12 +92,9 @@ __global__ __launch_bounds__(TPB) void k_lidar_project(Project a) {
       rigid(a.cam2_s + (long long)s * 12, x, y, z, X2, Y2, Z2);
     }
     const double* Kb = a.K + (long long)b * a.k_stride;
-    const double fx = Kb[0], cx = Kb[2], fy = Kb[4], cy = Kb[5];
-    o[0] = (fx * X1 + cx * Z1) / Z1; o[1] = (fy * Y1 + cy * Z1) / Z1; o[2] = Z1;        // view_points(normalize=True), :176
-    o[3] = (fx * X2 + cx * Z2) / Z2; o[4] = (fy * Y2 + cy * Z2) / Z2;
-    const bool far = fabs(x) >= a.min_dist || fabs(y) >= a.min_dist;       // remove_close: not (|x| < d and |y| < d)
-    ok = far && Z1 >= a.min_z && Z2 >= a.min_z && o[0] > 0.0 && o[0] < a.im_w && o[1] > 0.0 && o[1] < a.im_h &&
-         o[3] > 0.0 && o[3] < a.im_w && o[4] > 0.0 && o[4] < a.im_h;       // :175-178
+    const Cam c1 = pinhole(Kb, X1, Y1, Z1), c2 = pinhole(Kb, X2, Y2, Z2);                // view_points(normalize=True), :176
+    o[0] = c1.px; o[1] = c1.py; o[2] = c1.Z; o[3] = c2.px; o[4] = c2.py;
+    ok = far_enough(x, y, a.min_dist) && in_view(c1, a.min_z, a.im_w, a.im_h) && in_view(c2, a.min_z, a.im_w, a.im_h);      // :175-178
   } else {
     hit = -1;
   }
@@ -127,75 +104,13 @@ __global__ __launch_bounds__(TPB) void k_lidar_project(Project a) {
 }
 
 // ---- ground truth -------------------------------------------------------------------------------------------------------
-struct Raster {
-  const double *x1, *y1, *d1, *x2, *y2;
-  const unsigned char *low_h, *in_box;
-  const unsigned char* valid;        // NULL: every point
-  const int32_t* off;
-  const double* K;
-  int B, n, k_stride;
-  int h_out, w_new, y_cutoff;        // h_out = h_new - y_cutoff rows are kept
-  double s, x_hi, y_hi;              // downsample_scale, w_new - 1, h_new - 1
-};
-
-// fuse_lidar.py:293-301: pixel centres of the small image, clipped into it
-__device__ __forceinline__ double scaled(double v, double s, double hi) { return fmin(fmax((v + 0.5) / s - 0.5, 0.0), hi); }
-
-// The flat index of point p's pixel in the [B][h_out][w_new] images, or -1: the point is masked out, belongs to no frame, is one the
-// reference would raise on (non-finite) or read as an empty pixel (depth <= 0), or falls on a row above the cutoff.  :305 rounds half
-// to even (Python's round).
-__device__ __forceinline__ long long pixel_of(const Raster& r, int p) {
-  if (r.valid && !r.valid[p]) return -1;
-  const int b = frame_of(r.off, r.B, p);
-  if (b < 0) return -1;
-  const double x1 = r.x1[p], y1 = r.y1[p], d = r.d1[p];
-  if (!(finite_d(x1) && finite_d(y1) && finite_d(r.x2[p]) && finite_d(r.y2[p]) && finite_d(d) && d > 0.0)) return -1;
-  const int col = (int)rint(scaled(x1, r.s, r.x_hi));
-  const int row = (int)rint(scaled(y1, r.s, r.y_hi)) - r.y_cutoff;
-  if (row < 0) return -1;
-  return ((long long)b * r.h_out + row) * r.w_new + col;                // row < h_out, col < w_new: the clip
-}
-
-// Pass 0: the key images to all ones -- no point (winner), above every depth (key).  n_words 8-byte words from a 16-byte boundary.
-__global__ __launch_bounds__(TPB) void k_lidar_clear(unsigned long long* ws, long long n_words) {
-  const long long n_vec = n_words >> 1, t = (long long)blockIdx.x * TPB + threadIdx.x;
-  for (long long v = t; v < n_vec; v += (long long)gridDim.x * TPB)
-    reinterpret_cast<uint4*>(ws)[v] = make_uint4(NO_POINT, NO_POINT, NO_POINT, NO_POINT);
-  if ((n_words & 1) && t == 0) ws[n_words - 1] = ~0ull;
-}
-
-// Pass 1: the smallest depth of every pixel.  Positive doubles order as their bit patterns do, so an unsigned 64-bit minimum is exact
-// and does not depend on the order of arrival.  A key only ever falls, so a plain read that already shows a depth at or below this
-// point's settles it without an atomic: with three points to a pixel and more on near surfaces most points take that way out.
-__global__ __launch_bounds__(TPB) void k_lidar_min_depth(Raster r, unsigned long long* key) {
-  const int p = blockIdx.x * TPB + threadIdx.x;
-  if (p >= r.n) return;
-  const long long pix = pixel_of(r, p);
-  if (pix < 0) return;
-  const unsigned long long mine = (unsigned long long)__double_as_longlong(r.d1[p]);
-  if (__hip_atomic_load(key + pix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= mine) return;
-  __hip_atomic_fetch_min(key + pix, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Pass 2: among the points that have that depth the lowest index wins -- the reference's loop (:308-317) replaces on a strictly
-// smaller depth only, so the first of equal depths stays.
-__global__ __launch_bounds__(TPB) void k_lidar_min_index(Raster r, const unsigned long long* key, unsigned* winner) {
-  const int p = blockIdx.x * TPB + threadIdx.x;
-  if (p >= r.n) return;
-  const long long pix = pixel_of(r, p);
-  if (pix < 0) return;
-  if (key[pix] != (unsigned long long)__double_as_longlong(r.d1[p])) return;
-  if (__hip_atomic_load(winner + pix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= (unsigned)p) return;
-  __hip_atomic_fetch_min(winner + pix, (unsigned)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // The rectangle and depth bound of one box in the output map (:650-668), 32 bytes per box: column and row ranges (inclusive), d_max.
 struct Rect { int x0, x1, y0, y1; double d_max; double pad; };
 
 // One thread per box: corners fp64 [n][8][4] = x, y, depth, in_view.  The rectangle spans the in-view corners only, d_max all eight.
 // A box with no corner in view, or with a value the reference would raise on (a non-finite coordinate of an in-view corner), gets
 // an empty rectangle.
-__global__ __launch_bounds__(TPB) void k_lidar_boxes(const double* corners, int n, Raster r, Rect* rects) {
+__global__ __launch_bounds__(TPB) void k_lidar_boxes(const double* corners, int n, Zbuf r, Rect* rects) {
   const int j = blockIdx.x * TPB + threadIdx.x;
   if (j >= n) return;
   const double* c = corners + (long long)j * 32;
@@ -207,8 +122,8 @@ __global__ __launch_bounds__(TPB) void k_lidar_boxes(const double* corners, int 
     if (c[4 * i + 3] != 0.0) {
       any = true;
       bad = bad || !(finite_d(x) && finite_d(y));
-      const double xs = fmin(fmax((x + 0.5) / r.s - 0.5, 0.0), r.x_hi);
-      const double ys = fmin(fmax(((y + 0.5) / r.s - 0.5) - (double)r.y_cutoff, 0.0), (double)(r.h_out - 1));
+      const double xs = scaled(x, r.s, r.x_hi);
+      const double ys = fmin(fmax(to_small(y, r.s) - (double)r.y_cutoff, 0.0), (double)(r.h_out - 1));
       xlo = fmin(xlo, xs); xhi = fmax(xhi, xs); ylo = fmin(ylo, ys); yhi = fmax(yhi, ys);
     }
   }
@@ -225,17 +140,16 @@ struct Filters {
   int n_boxes;
   const float* flow_im;              // NULL: no flow filter
   double thres;
+  const unsigned char *low_h, *in_box;         // per point, from the projection
 };
 
 // What is left of a won pixel after both filters, and its u, v (:571-598).  pix is its flat index, i its winner.
-__device__ __forceinline__ void resolve_one(const Raster& r, const Filters& f, long long pix, unsigned i, float& depth, float& u, float& v,
+__device__ __forceinline__ void resolve_one(const Zbuf& r, const Filters& f, long long pix, unsigned i, float& depth, float& u, float& v,
                                             unsigned char& lh) {
-  const long long per = (long long)r.h_out * r.w_new;
-  const int b = (int)(pix / per);
-  const int rem = (int)(pix - b * per);
-  const int row = rem / r.w_new, col = rem - row * r.w_new;
+  const Pixel a = pixel_at(r, pix);
+  const int b = a.b, row = a.row, col = a.col;         // (as locals: through `a` the kernel, at its SGPR limit, spills scalars into vector lanes)
   const double d = r.d1[i];
-  if (f.seg && f.seg[pix] && !r.in_box[i]) {                               // :672
+  if (f.seg && f.seg[pix] && !f.in_box[i]) {                               // :672
     int j0 = f.box_off[b], j1 = f.box_off[b + 1];
     j0 = j0 < 0 ? 0 : j0;
     j1 = j1 > f.n_boxes ? f.n_boxes : j1;
@@ -244,26 +158,20 @@ __device__ __forceinline__ void resolve_one(const Raster& r, const Filters& f, l
       if (col >= q.x0 && col <= q.x1 && row >= q.y0 && row <= q.y1 && d > q.d_max) return;
     }
   }
-  const double xa = scaled(r.x1[i], r.s, r.x_hi), ya = scaled(r.y1[i], r.s, r.y_hi);
-  const double xb = scaled(r.x2[i], r.s, r.x_hi), yb = scaled(r.y2[i], r.s, r.y_hi);
-  const double fx_ = xb - xa, fy_ = yb - ya;                               // :310
+  double fx_, fy_;                                                         // :310
+  flow_of(r, i, fx_, fy_);
   if (f.flow_im) {                                                         // :557-560
     const double ex = fx_ - (double)f.flow_im[pix * 2], ey = fy_ - (double)f.flow_im[pix * 2 + 1];
     if (sqrt(ex * ex + ey * ey) > f.thres) return;
   }
-  const float xm = (float)((double)col + fx_);                             // x_map is float32 (:581-582); the sum is rounded once into it
-  const float ym = (float)((double)row + fy_);
-  const double* Kb = r.K + (long long)b * r.k_stride;
-  const double fl = Kb[0] / r.s, cx = Kb[2] / r.s, cy = Kb[5] / r.s - (double)r.y_cutoff;      // :585-587; fx divides both (:589-590)
   depth = (float)d;
-  u = (float)(((double)xm - cx) / fl);
-  v = (float)(((double)ym - cy) / fl);
-  lh = r.low_h[i] ? 1 : 0;
+  flow_uv(r, a, fx_, fy_, u, v);                                       // :581-590
+  lh = f.low_h[i] ? 1 : 0;
 }
 
 // Pass 3: every pixel of gt [.][3], depth and msk_lh, four pixels per thread.  A winner is an index below n (NO_POINT is not): nothing
 // read from the image is trusted.
-__global__ __launch_bounds__(TPB) void k_lidar_resolve(Raster r, Filters f, const unsigned* winner, long long n_pix, float* gt, float* depth,
+__global__ __launch_bounds__(TPB) void k_lidar_resolve(Zbuf r, Filters f, const unsigned* winner, long long n_pix, float* gt, float* depth,
                                                        unsigned char* msk) {
   const long long n_quads = (n_pix + 3) >> 2;
   for (long long q = (long long)blockIdx.x * TPB + threadIdx.x; q < n_quads; q += (long long)gridDim.x * TPB) {
@@ -281,10 +189,7 @@ __global__ __launch_bounds__(TPB) void k_lidar_resolve(Raster r, Filters f, cons
             dep[k] = o[3 * k];
           }
       }
-      float4* dst = reinterpret_cast<float4*>(gt + p0 * 3);
-      dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-      dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-      dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+      store_quad3(gt, p0, o);
       *reinterpret_cast<float4*>(depth + p0) = make_float4(dep[0], dep[1], dep[2], dep[3]);
       *reinterpret_cast<unsigned*>(msk + p0) = (unsigned)lh[0] | ((unsigned)lh[1] << 8) | ((unsigned)lh[2] << 16) | ((unsigned)lh[3] << 24);
     } else {                                                              // the last, short quad
@@ -301,7 +206,6 @@ __global__ __launch_bounds__(TPB) void k_lidar_resolve(Raster r, Filters f, cons
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline double from_bits(uint64_t b) { double d; memcpy(&d, &b, 8); return d; }
 
 }  // namespace
@@ -348,51 +252,29 @@ extern "C" int crd_lidar_ground_truth(const double* x1, const double* y1, const 
                                       const int32_t* corner_offsets, int32_t n_boxes, const float* flow_im, uint64_t thres_f64_bits,
                                       void* workspace, int64_t workspace_bytes, float* gt, float* depth, uint8_t* msk_lh,
                                       crd_stream_t stream) {
-  CRD_CHECK_ARG(B > 0 && B <= 65535 && n_points >= 0 && n_boxes >= 0 && im_h > 0 && im_w > 0 && downsample_scale > 0,
-                "crd_lidar_ground_truth: bad argument (B %d, n_points %d, n_boxes %d, image %d x %d, downsample_scale %d)", B, n_points,
-                n_boxes, im_h, im_w, downsample_scale);
-  const int h_new = im_h / downsample_scale, w_new = im_w / downsample_scale;
-  CRD_CHECK_ARG(h_new > 0 && w_new > 0, "crd_lidar_ground_truth: bad argument (downsample_scale %d leaves no pixel of %d x %d)",
-                downsample_scale, im_h, im_w);
-  CRD_CHECK_ARG(y_cutoff >= 0 && y_cutoff < h_new, "crd_lidar_ground_truth: bad argument (y_cutoff %d outside [0, %d))", y_cutoff, h_new);
-  CRD_CHECK_ARG(k_stride == 0 || k_stride == 9, "crd_lidar_ground_truth: bad argument (k_stride %d is neither 0 nor 9)", k_stride);
+  CRD_CHECK_ARG(n_boxes >= 0, "crd_lidar_ground_truth: bad argument (n_boxes %d)", n_boxes);
   const double thres = from_bits(thres_f64_bits);
   CRD_CHECK_ARG(!flow_im || thres == thres, "crd_lidar_ground_truth: bad argument (thres is NaN)");
-  CRD_CHECK_ARG(K && workspace && gt && depth && msk_lh, "crd_lidar_ground_truth: null pointer");
-  CRD_CHECK_ARG(n_points == 0 || (x1 && y1 && depth1 && x2 && y2 && low_h && in_box && frame_offsets),
-                "crd_lidar_ground_truth: null pointer (points)");
+  CRD_CHECK_ARG(gt && depth && msk_lh && (n_points == 0 || (low_h && in_box)),
+                "crd_lidar_ground_truth: null pointer (gt, depth, msk_lh, low_h, in_box)");
   CRD_CHECK_ARG((seg != nullptr) == (corner_offsets != nullptr) && (!seg || n_boxes == 0 || corners),
                 "crd_lidar_ground_truth: bad argument (the box filter takes seg, corners and corner_offsets together)");
-  const int h_out = h_new - y_cutoff;
-  const long long n_pix = (long long)B * h_out * w_new;
-  const long long key_off = (n_pix * 4 + 15) & ~15ll, rect_off = (key_off + n_pix * 8 + 15) & ~15ll;
-  const long long need = rect_off + (seg ? 32ll * n_boxes : 0ll);
-  CRD_CHECK_ARG(workspace_bytes >= need, "crd_lidar_ground_truth: the workspace holds %lld bytes, %lld are needed",
-                (long long)workspace_bytes, need);
-  CRD_CHECK_ARG(aligned16(workspace) && aligned16(gt) && aligned16(depth) && (reinterpret_cast<uintptr_t>(msk_lh) & 3) == 0,
-                "crd_lidar_ground_truth: bad argument (workspace, gt and depth must be 16-byte aligned, msk_lh 4-byte aligned)");
+  CRD_CHECK_ARG(aligned16(gt) && aligned16(depth) && (reinterpret_cast<uintptr_t>(msk_lh) & 3) == 0,
+                "crd_lidar_ground_truth: bad argument (gt and depth must be 16-byte aligned, msk_lh 4-byte aligned)");
   hipStream_t st = as_stream(stream);
-  unsigned* winner = reinterpret_cast<unsigned*>(workspace);
-  unsigned long long* key = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + key_off);
-  Rect* rects = reinterpret_cast<Rect*>(reinterpret_cast<char*>(workspace) + rect_off);
-  const long long clear_words = rect_off / 8, clear_blocks = (clear_words / 2 + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_lidar_clear, dim3((unsigned)(clear_blocks < 2048 ? (clear_blocks > 0 ? clear_blocks : 1) : 2048)), dim3(TPB), 0, st,
-                     reinterpret_cast<unsigned long long*>(workspace), clear_words);
-  Raster r;
-  r.x1 = x1; r.y1 = y1; r.d1 = depth1; r.x2 = x2; r.y2 = y2; r.low_h = low_h; r.in_box = in_box; r.valid = valid;
-  r.off = frame_offsets; r.K = K; r.B = B; r.n = n_points; r.k_stride = k_stride; r.h_out = h_out; r.w_new = w_new;
-  r.y_cutoff = y_cutoff; r.s = (double)downsample_scale; r.x_hi = (double)(w_new - 1); r.y_hi = (double)(h_new - 1);
+  Zbuf r;
+  r.x1 = x1; r.y1 = y1; r.d1 = depth1; r.x2 = x2; r.y2 = y2; r.extra = nullptr; r.valid = valid; r.off = frame_offsets; r.K = K;
+  ZbufImages im;
+  const long long rect_bytes = seg ? 32ll * n_boxes : 0ll;                 // the rectangles lie behind the key images, from a 16-byte boundary
+  const int rc = zbuf_passes("crd_lidar_ground_truth", r, B, n_points, k_stride, im_h, im_w, downsample_scale, y_cutoff, workspace,
+                             workspace_bytes, [=](long long key_end) { return ((key_end + 15) & ~15ll) + rect_bytes; }, st, im);
+  if (rc != CRD_OK) return rc;
   Filters f;
-  f.seg = seg; f.rects = rects; f.box_off = corner_offsets; f.n_boxes = n_boxes; f.flow_im = flow_im; f.thres = thres;
+  f.low_h = low_h; f.in_box = in_box; f.seg = seg; f.box_off = corner_offsets; f.n_boxes = n_boxes; f.flow_im = flow_im; f.thres = thres;
+  Rect* rects = reinterpret_cast<Rect*>(reinterpret_cast<char*>(workspace) + ((im.key_end + 15) & ~15ll));
+  f.rects = rects;
   if (seg && n_boxes > 0) hipLaunchKernelGGL(k_lidar_boxes, dim3(cdiv(n_boxes, TPB)), dim3(TPB), 0, st, corners, n_boxes, r, rects);
-  if (n_points > 0) {
-    hipLaunchKernelGGL(k_lidar_min_depth, dim3(cdiv(n_points, TPB)), dim3(TPB), 0, st, r, key);
-    hipLaunchKernelGGL(k_lidar_min_index, dim3(cdiv(n_points, TPB)), dim3(TPB), 0, st, r, key, winner);
-  }
-  const long long n_quads = (n_pix + 3) / 4;
-  const long long blocks = (n_quads + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_lidar_resolve, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(TPB), 0, st, r, f, winner, n_pix, gt, depth,
-                     msk_lh);
+  hipLaunchKernelGGL(k_lidar_resolve, dim3(quad_blocks(im.n_pix)), dim3(TPB), 0, st, r, f, im.winner, im.n_pix, gt, depth, msk_lh);
   CRD_LAUNCH_CHECK("crd_lidar_ground_truth");
   return CRD_OK;
 }

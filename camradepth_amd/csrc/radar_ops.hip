@@ -2,42 +2,21 @@
 // reads.  Two stages of the reference's offline preprocessing (lib/fuse_radar.py): the projection nested in merge_selected_radar
 // (:30-74, :144-151) and the rasteriser cal_depthMap_flow (:156-204) + radarFlow2uv (:276-303).  All arithmetic is fp64, as NumPy's.
 // The input is a few thousand detections; the only pass that touches every pixel is the resolve at the end.
-#include "common.h"
+#include "raster.h"       // the projection arithmetic, the z-buffer passes and the helpers of the resolve pass are shared with lidar_ops.hip
 
 // the rasteriser is pinned bit for bit to NumPy, which never fuses a multiply into an add
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr unsigned NO_POINT = 0xffffffffu;
+constexpr int TPB = ZBUF_TPB;
 
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < INFINITY; }      // false for NaN as well
-
-// The frame of point p: the b with off[b] <= p < off[b + 1], or -1.  off has B + 1 non-decreasing entries (empty frames repeat a value).
-__device__ __forceinline__ int frame_of(const int32_t* off, int B, int p) {
-  int lo = 0, hi = B + 1;                      // first j in [0, B + 1] with off[j] > p
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] > p) hi = mid; else lo = mid + 1;
-  }
-  return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
-
-struct Cam { double px, py, Z; };
-
-// fuse_radar.py:49-52 (Doppler compensation, then the pose chain) and view_points(..., normalize=True) of :69: K . (X, Y, Z) / Z
-__device__ __forceinline__ Cam project_one(const double* M, double lag, double x, double y, double z, double vx, double vy,
-                                           double fx, double fy, double cx, double cy) {
+// fuse_radar.py:49-52 (Doppler compensation, then the pose chain) and view_points(..., normalize=True) of :69
+__device__ __forceinline__ Cam project_one(const double* M, double lag, double x, double y, double z, double vx, double vy, const double* Kb) {
   const double xs = x + vx * lag, ys = y + vy * lag;
-  const double X = M[0] * xs + M[1] * ys + M[2] * z + M[3];
-  const double Y = M[4] * xs + M[5] * ys + M[6] * z + M[7];
-  const double Z = M[8] * xs + M[9] * ys + M[10] * z + M[11];
-  Cam c;
-  c.px = (fx * X + cx * Z) / Z;
-  c.py = (fy * Y + cy * Z) / Z;
-  c.Z = Z;
-  return c;
+  double X, Y, Z;
+  rigid(M, xs, ys, z, X, Y, Z);
+  return pinhole(Kb, X, Y, Z);
 }
 
 // One thread per point.  Every comparison is written so that a NaN fails it (:68, :73); a NaN coordinate that passes remove_close (:32)
@@ -57,97 +36,30 @@ __global__ __launch_bounds__(TPB) void k_radar_project(const double* pts, const 
     const double* q = pts + (long long)p * 5;
     const double x = q[0], y = q[1], z = q[2], vx = q[3], vy = q[4];
     const double* Kb = K + (long long)b * k_stride;
-    const double fx = Kb[0], cx = Kb[2], fy = Kb[4], cy = Kb[5];
-    const Cam a = project_one(M1 + (long long)s * 12, lags[2 * s], x, y, z, vx, vy, fx, fy, cx, cy);
-    const Cam c = project_one(M2 + (long long)s * 12, lags[2 * s + 1], x, y, z, vx, vy, fx, fy, cx, cy);
+    const Cam a = project_one(M1 + (long long)s * 12, lags[2 * s], x, y, z, vx, vy, Kb);
+    const Cam c = project_one(M2 + (long long)s * 12, lags[2 * s + 1], x, y, z, vx, vy, Kb);
     o[0] = a.px; o[1] = a.py; o[2] = a.Z; o[3] = c.px; o[4] = c.py;
     o[5] = sqrt(vx * vx + vy * vy);
-    const bool far = fabs(x) >= min_dist || fabs(y) >= min_dist;          // not (|x| < d and |y| < d)
-    ok = far && a.Z >= min_z && c.Z >= min_z && a.px > 0.0 && a.px < im_w && a.py > 0.0 && a.py < im_h &&
-         c.px > 0.0 && c.px < im_w && c.py > 0.0 && c.py < im_h;
+    ok = far_enough(x, y, min_dist) && in_view(a, min_z, im_w, im_h) && in_view(c, min_z, im_w, im_h);
   }
   x1[p] = o[0]; y1[p] = o[1]; d1[p] = o[2]; x2[p] = o[3]; y2[p] = o[4]; vc[p] = o[5];
   valid[p] = ok ? 1 : 0;
 }
 
 // ---- rasteriser ---------------------------------------------------------------------------------------------------------
-struct Raster {
-  const double *x1, *y1, *d1, *x2, *y2, *vc;
-  const unsigned char* valid;        // NULL: every point
-  const int32_t* off;
-  const double* K;
-  int B, n, k_stride;
-  int h_out, w_new, y_cutoff;        // h_out = h_new - y_cutoff rows are kept
-  double s, x_hi, y_hi;              // downsample_scale, w_new - 1, h_new - 1
-};
-
-// fuse_radar.py:169-177: pixel centres of the small image, clipped into it
-__device__ __forceinline__ double scaled(double v, double s, double hi) { return fmin(fmax((v + 0.5) / s - 0.5, 0.0), hi); }
-
-// The flat index of point p's pixel in the [B][h_out][w_new] images, or -1: the point is masked out, belongs to no frame, is one the
-// reference would raise on (non-finite, depth <= 0), or falls on a row above the cutoff.  :183 rounds half to even (Python's round).
-__device__ __forceinline__ long long pixel_of(const Raster& r, int p) {
-  if (r.valid && !r.valid[p]) return -1;
-  const int b = frame_of(r.off, r.B, p);
-  if (b < 0) return -1;
-  const double x1 = r.x1[p], y1 = r.y1[p], d = r.d1[p];
-  if (!(finite_d(x1) && finite_d(y1) && finite_d(r.x2[p]) && finite_d(r.y2[p]) && finite_d(r.vc[p]) && finite_d(d) && d > 0.0)) return -1;
-  const int col = (int)rint(scaled(x1, r.s, r.x_hi));
-  const int row = (int)rint(scaled(y1, r.s, r.y_hi)) - r.y_cutoff;
-  if (row < 0) return -1;
-  return ((long long)b * r.h_out + row) * r.w_new + col;                // row < h_out, col < w_new: the clip
-}
-
-// Pass 0: both key images to all ones -- no point (winner), above every depth (key).  n_words 8-byte words from a 16-byte boundary.
-__global__ __launch_bounds__(TPB) void k_radar_clear(unsigned long long* ws, long long n_words) {
-  const long long n_vec = n_words >> 1, t = (long long)blockIdx.x * TPB + threadIdx.x;
-  for (long long v = t; v < n_vec; v += (long long)gridDim.x * TPB)
-    reinterpret_cast<uint4*>(ws)[v] = make_uint4(NO_POINT, NO_POINT, NO_POINT, NO_POINT);
-  if ((n_words & 1) && t == 0) ws[n_words - 1] = ~0ull;
-}
-
-// Pass 1: the smallest depth of every pixel.  Positive doubles order as their bit patterns do, so an unsigned 64-bit minimum is exact
-// and does not depend on the order of arrival.
-__global__ __launch_bounds__(TPB) void k_radar_min_depth(Raster r, unsigned long long* key) {
-  const int p = blockIdx.x * TPB + threadIdx.x;
-  if (p >= r.n) return;
-  const long long pix = pixel_of(r, p);
-  if (pix < 0) return;
-  __hip_atomic_fetch_min(key + pix, (unsigned long long)__double_as_longlong(r.d1[p]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Pass 2: among the points that have that depth the lowest index wins -- the reference's loop (:185-197) replaces on a strictly
-// smaller depth only, so the first of equal depths stays.
-__global__ __launch_bounds__(TPB) void k_radar_min_index(Raster r, const unsigned long long* key, unsigned* winner) {
-  const int p = blockIdx.x * TPB + threadIdx.x;
-  if (p >= r.n) return;
-  const long long pix = pixel_of(r, p);
-  if (pix < 0) return;
-  if (key[pix] == (unsigned long long)__double_as_longlong(r.d1[p]))
-    __hip_atomic_fetch_min(winner + pix, (unsigned)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The four values of a won pixel (:187, :202, :284-295).  pix is its flat index.
-__device__ __forceinline__ void resolve_one(const Raster& r, long long pix, unsigned i, float& depth, float& u, float& v, float& vel) {
-  const long long per = (long long)r.h_out * r.w_new;
-  const int b = (int)(pix / per);
-  const int rem = (int)(pix - b * per);
-  const int row = rem / r.w_new, col = rem - row * r.w_new;
-  const double xa = scaled(r.x1[i], r.s, r.x_hi), ya = scaled(r.y1[i], r.s, r.y_hi);
-  const double xb = scaled(r.x2[i], r.s, r.x_hi), yb = scaled(r.y2[i], r.s, r.y_hi);
-  const float xm = (float)((double)col + (xb - xa));                     // x_map is float32 (:286); the sum is rounded once into it
-  const float ym = (float)((double)row + (yb - ya));
-  const double* Kb = r.K + (long long)b * r.k_stride;
-  const double f = Kb[0] / r.s, cx = Kb[2] / r.s, cy = Kb[5] / r.s - (double)r.y_cutoff;      // :290-292; f is fx for both (:294-295)
+// The four values of a won pixel (:187, :202, :284-295).  pix is its flat index, i its winner; r.extra is v_comp.
+__device__ __forceinline__ void resolve_one(const Zbuf& r, long long pix, unsigned i, float& depth, float& u, float& v, float& vel) {
+  const Pixel a = pixel_at(r, pix);
+  double fx, fy;
+  flow_of(r, i, fx, fy);
   depth = (float)r.d1[i];
-  u = (float)(((double)xm - cx) / f);
-  v = (float)(((double)ym - cy) / f);
-  vel = r.vc[i] > 0.5 ? 1.f : 0.f;
+  flow_uv(r, a, fx, fy, u, v);
+  vel = r.extra[i] > 0.5 ? 1.f : 0.f;
 }
 
 // Pass 3: every pixel of radar [.][3] and rad_vel, four pixels (64 bytes out, 16 in) per thread; a quad nobody won is four vector stores
 // of zeros, and almost every quad is one.  A winner is an index below n (NO_POINT is not): nothing read from the image is trusted.
-__global__ __launch_bounds__(TPB) void k_radar_resolve(Raster r, const unsigned* winner, long long n_pix, float* radar, float* rad_vel) {
+__global__ __launch_bounds__(TPB) void k_radar_resolve(Zbuf r, const unsigned* winner, long long n_pix, float* radar, float* rad_vel) {
   const long long n_quads = (n_pix + 3) >> 2;
   for (long long q = (long long)blockIdx.x * TPB + threadIdx.x; q < n_quads; q += (long long)gridDim.x * TPB) {
     const long long p0 = q * 4;
@@ -160,10 +72,7 @@ __global__ __launch_bounds__(TPB) void k_radar_resolve(Raster r, const unsigned*
         for (int k = 0; k < 4; ++k)
           if (wi[k] < (unsigned)r.n) resolve_one(r, p0 + k, wi[k], o[3 * k], o[3 * k + 1], o[3 * k + 2], vel[k]);
       }
-      float4* dst = reinterpret_cast<float4*>(radar + p0 * 3);
-      dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-      dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-      dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+      store_quad3(radar, p0, o);
       *reinterpret_cast<float4*>(rad_vel + p0) = make_float4(vel[0], vel[1], vel[2], vel[3]);
     } else {                                                              // the last, short quad
       for (long long p = p0; p < n_pix; ++p) {
@@ -176,8 +85,6 @@ __global__ __launch_bounds__(TPB) void k_radar_resolve(Raster r, const unsigned*
     }
   }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -207,40 +114,16 @@ extern "C" int crd_radar_rasterize(const double* x1, const double* y1, const dou
                                    const double* K, int32_t k_stride, int32_t im_h, int32_t im_w, int32_t downsample_scale,
                                    int32_t y_cutoff, void* workspace, int64_t workspace_bytes, float* radar, float* rad_vel,
                                    crd_stream_t stream) {
-  CRD_CHECK_ARG(B > 0 && B <= 65535 && n_points >= 0 && im_h > 0 && im_w > 0 && downsample_scale > 0,
-                "crd_radar_rasterize: bad argument (B %d, n_points %d, image %d x %d, downsample_scale %d)", B, n_points, im_h, im_w,
-                downsample_scale);
-  const int h_new = im_h / downsample_scale, w_new = im_w / downsample_scale;
-  CRD_CHECK_ARG(h_new > 0 && w_new > 0, "crd_radar_rasterize: bad argument (downsample_scale %d leaves no pixel of %d x %d)",
-                downsample_scale, im_h, im_w);
-  CRD_CHECK_ARG(y_cutoff >= 0 && y_cutoff < h_new, "crd_radar_rasterize: bad argument (y_cutoff %d outside [0, %d))", y_cutoff, h_new);
-  CRD_CHECK_ARG(k_stride == 0 || k_stride == 9, "crd_radar_rasterize: bad argument (k_stride %d is neither 0 nor 9)", k_stride);
-  CRD_CHECK_ARG(K && workspace && radar && rad_vel, "crd_radar_rasterize: null pointer");
-  CRD_CHECK_ARG(n_points == 0 || (x1 && y1 && depth1 && x2 && y2 && v_comp && frame_offsets), "crd_radar_rasterize: null pointer (points)");
-  const int h_out = h_new - y_cutoff;
-  const long long n_pix = (long long)B * h_out * w_new;
-  const long long key_off = (n_pix * 4 + 15) & ~15ll, need = key_off + n_pix * 8;
-  CRD_CHECK_ARG(workspace_bytes >= need, "crd_radar_rasterize: the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes,
-                need);
-  CRD_CHECK_ARG(aligned16(workspace) && aligned16(radar) && aligned16(rad_vel),
-                "crd_radar_rasterize: bad argument (workspace, radar and rad_vel must be 16-byte aligned)");
+  CRD_CHECK_ARG(radar && rad_vel && (n_points == 0 || v_comp), "crd_radar_rasterize: null pointer (radar, rad_vel, v_comp)");
+  CRD_CHECK_ARG(aligned16(radar) && aligned16(rad_vel), "crd_radar_rasterize: bad argument (radar and rad_vel must be 16-byte aligned)");
   hipStream_t st = as_stream(stream);
-  unsigned* winner = reinterpret_cast<unsigned*>(workspace);
-  unsigned long long* key = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + key_off);
-  const long long clear_blocks = (need / 16 + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_radar_clear, dim3((unsigned)(clear_blocks < 2048 ? (clear_blocks > 0 ? clear_blocks : 1) : 2048)), dim3(TPB), 0, st,
-                     reinterpret_cast<unsigned long long*>(workspace), need / 8);
-  Raster r;
-  r.x1 = x1; r.y1 = y1; r.d1 = depth1; r.x2 = x2; r.y2 = y2; r.vc = v_comp; r.valid = valid; r.off = frame_offsets; r.K = K;
-  r.B = B; r.n = n_points; r.k_stride = k_stride; r.h_out = h_out; r.w_new = w_new; r.y_cutoff = y_cutoff;
-  r.s = (double)downsample_scale; r.x_hi = (double)(w_new - 1); r.y_hi = (double)(h_new - 1);
-  if (n_points > 0) {
-    hipLaunchKernelGGL(k_radar_min_depth, dim3(cdiv(n_points, TPB)), dim3(TPB), 0, st, r, key);
-    hipLaunchKernelGGL(k_radar_min_index, dim3(cdiv(n_points, TPB)), dim3(TPB), 0, st, r, key, winner);
-  }
-  const long long n_quads = (n_pix + 3) / 4;
-  const long long blocks = (n_quads + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_radar_resolve, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(TPB), 0, st, r, winner, n_pix, radar, rad_vel);
+  Zbuf r;
+  r.x1 = x1; r.y1 = y1; r.d1 = depth1; r.x2 = x2; r.y2 = y2; r.extra = v_comp; r.valid = valid; r.off = frame_offsets; r.K = K;
+  ZbufImages im;
+  const int rc = zbuf_passes("crd_radar_rasterize", r, B, n_points, k_stride, im_h, im_w, downsample_scale, y_cutoff, workspace,
+                             workspace_bytes, [](long long key_end) { return key_end; }, st, im);
+  if (rc != CRD_OK) return rc;
+  hipLaunchKernelGGL(k_radar_resolve, dim3(quad_blocks(im.n_pix)), dim3(TPB), 0, st, r, im.winner, im.n_pix, radar, rad_vel);
   CRD_LAUNCH_CHECK("crd_radar_rasterize");
   return CRD_OK;
 }

@@ -11,11 +11,12 @@ frame_offsets[b] .. frame_offsets[b + 1] - 1."""
 import torch
 
 from . import lib as L
-from .radar import _dev, _frames, _intrinsics, _size, map_shape
+from ._frontend import RasterWorkspace, _dev, _frames, _intrinsics, _size, map_shape, raster_args
 
 PROJ_KEYS = ("x1", "y1", "depth1", "x2", "y2")
 FLAG_KEYS = ("low_h", "in_box", "valid")
 ENTRY = 15               # doubles per box entry: box_from_sensor [3][4], then l/2, w/2, h/2
+OUT_SPEC = {"gt": (torch.float32, (3,)), "depth": (torch.float32, ()), "msk_lh": (torch.uint8, ())}
 
 
 def workspace_bytes(n_pix, n_boxes=0):
@@ -24,32 +25,17 @@ def workspace_bytes(n_pix, n_boxes=0):
     return ((((4 * n_pix + 15) & ~15) + 8 * n_pix + 15) & ~15) + 32 * n_boxes
 
 
-class LidarWorkspace:
+class LidarWorkspace(RasterWorkspace):
     """The scratch memory of the front end for batches of up to B frames: the per-pixel key images of the rasteriser (sized for
     y_cutoff = 0, so any cutoff fits), room for the rectangles of up to max_boxes boxes and, with max_points given, the projection's
     outputs for up to that many points.  With workspace= and out= a call allocates nothing, so it can be captured in a graph on one
     stream."""
+    GROUPS = (("proj", torch.float64, PROJ_KEYS), ("flags", torch.uint8, FLAG_KEYS), ("box_entry", torch.int32, None))
 
     def __init__(self, B, image_size=(900, 1600), downsample_scale=2, max_points=None, max_boxes=0, device="cuda"):
-        h, w = map_shape(image_size, downsample_scale, 0)
-        if int(B) <= 0 or int(max_boxes) < 0:
-            raise L.CrdError(f"LidarWorkspace: B = {B}, max_boxes = {max_boxes}")
-        self.B, self.image_size, self.downsample_scale = int(B), _size(image_size), int(downsample_scale)
-        self.keys = torch.empty(workspace_bytes(self.B * h * w, int(max_boxes)), dtype=torch.uint8, device=device)
-        self.max_points = None if max_points is None else int(max_points)
-        if self.max_points is not None:
-            self.proj = torch.empty(len(PROJ_KEYS), self.max_points, dtype=torch.float64, device=device)
-            self.flags = torch.empty(len(FLAG_KEYS), self.max_points, dtype=torch.uint8, device=device)
-            self.box_entry = torch.empty(self.max_points, dtype=torch.int32, device=device)
-
-    def proj_out(self, n):
-        """The projection buffers for n points, as project_lidar(out=) takes them."""
-        if self.max_points is None or n > self.max_points:
-            raise L.CrdError(f"LidarWorkspace: no room for the projection of {n} points (max_points = {self.max_points})")
-        out = {k: self.proj[i, :n] for i, k in enumerate(PROJ_KEYS)}
-        out.update({k: self.flags[i, :n] for i, k in enumerate(FLAG_KEYS)})
-        out["box_entry"] = self.box_entry[:n]
-        return out
+        if int(max_boxes) < 0:
+            raise L.CrdError(f"LidarWorkspace: max_boxes = {max_boxes}")
+        super().__init__(B, image_size, downsample_scale, max_points, lambda n_pix: workspace_bytes(n_pix, int(max_boxes)), device)
 
 
 def project_lidar(points, sweep_index, frame_offsets, cam1_from_sensor, cam2_from_sensor, car_z_from_sensor, K, sweep_boxes=None,
@@ -137,48 +123,23 @@ def lidar_ground_truth(proj, frame_offsets, K, image_size=(900, 1600), downsampl
     flow_im [B,h,w,2] fp32 and thres.  Returns {'gt': [B,h,w,3] fp32 = depth, u, v; 'depth': [B,h,w] fp32, what
     assemble_batch(gt_depth=) takes; 'msk_lh': [B,h,w] uint8} with (h, w) = map_shape(...).  workspace: a LidarWorkspace; out: a
     dictionary of the three tensors to write into."""
-    off, B = _frames(frame_offsets)
-    if not all(k in proj for k in PROJ_KEYS + ("low_h", "in_box")):
-        raise L.CrdError(f"lidar_ground_truth: proj needs {PROJ_KEYS + ('low_h', 'in_box')}")
-    N = proj["x1"].shape[0] if torch.is_tensor(proj["x1"]) and proj["x1"].dim() == 1 else None
-    p = [_dev(proj[k], torch.float64, (N,), f"proj['{k}']") for k in PROJ_KEYS]
-    flags = [_dev(proj[k], torch.uint8, (N,), f"proj['{k}']") for k in ("low_h", "in_box")]
-    valid = proj.get("valid")
-    if valid is not None:
-        valid = _dev(valid, torch.uint8, (N,), "proj['valid']")
-    K, k_stride = _intrinsics(K, B)
-    im_h, im_w = _size(image_size)
-    h, w = map_shape(image_size, downsample_scale, y_cutoff)
-    Nb = 0
-    if seg is not None or corners is not None or corner_offsets is not None:
+    fn = "lidar_ground_truth"
+    Nb, box_filter = 0, seg is not None or corners is not None or corner_offsets is not None
+    if box_filter:
         if seg is None or corners is None or corner_offsets is None:
-            raise L.CrdError("lidar_ground_truth: the box filter takes seg, corners and corner_offsets together")
-        seg = _dev(seg, torch.uint8, (B, h, w), "seg")
+            raise L.CrdError(f"{fn}: the box filter takes seg, corners and corner_offsets together")
         corners = _dev(corners, torch.float64, (None, 8, 4), "corners")
         Nb = corners.shape[0]
+    head, keys, out, B, h, w = raster_args(fn, proj, frame_offsets, K, image_size, downsample_scale, y_cutoff, PROJ_KEYS, ("low_h", "in_box"),
+                                           workspace, lambda n_pix: workspace_bytes(n_pix, Nb), out, OUT_SPEC, detail=f", {Nb} boxes")
+    if box_filter:
+        seg = _dev(seg, torch.uint8, (B, h, w), "seg")
         corner_offsets = _dev(corner_offsets, torch.int32, (B + 1,), "corner_offsets")
     if flow_im is not None:
         flow_im = _dev(flow_im, torch.float32, (B, h, w, 2), "flow_im")
-    need = workspace_bytes(B * h * w, Nb)
-    if workspace is None:
-        keys = torch.empty(need, dtype=torch.uint8, device=p[0].device)
-    else:
-        keys = workspace.keys
-        if keys.numel() < need:
-            raise L.CrdError(f"lidar_ground_truth: the workspace holds {keys.numel()} bytes, {need} are needed "
-                             f"(B {B}, image {im_h} x {im_w}, downsample_scale {downsample_scale}, {Nb} boxes)")
-    if out is None:
-        out = {"gt": torch.empty(B, h, w, 3, device=p[0].device), "depth": torch.empty(B, h, w, device=p[0].device),
-               "msk_lh": torch.empty(B, h, w, dtype=torch.uint8, device=p[0].device)}
-    else:
-        out = {"gt": _dev(out["gt"], torch.float32, (B, h, w, 3), "out['gt']"),
-               "depth": _dev(out["depth"], torch.float32, (B, h, w), "out['depth']"),
-               "msk_lh": _dev(out["msk_lh"], torch.uint8, (B, h, w), "out['msk_lh']")}
     L.check(L.load().crd_lidar_ground_truth(
-        *(L.ptr(t) for t in p), *(L.ptr(t) for t in flags), L.ptr(valid), L.ptr(off), B, N, L.ptr(K), k_stride, im_h, im_w,
-        int(downsample_scale), int(y_cutoff), L.ptr(seg), L.ptr(corners) if Nb else None, L.ptr(corner_offsets), Nb, L.ptr(flow_im),
-        L.f64_bits(thres), L.ptr(keys), keys.numel(), L.ptr(out["gt"]), L.ptr(out["depth"]), L.ptr(out["msk_lh"]), L.stream()),
-        "crd_lidar_ground_truth")
+        *head, L.ptr(seg), L.ptr(corners) if Nb else None, L.ptr(corner_offsets), Nb, L.ptr(flow_im), L.f64_bits(thres), L.ptr(keys),
+        keys.numel(), L.ptr(out["gt"]), L.ptr(out["depth"]), L.ptr(out["msk_lh"]), L.stream()), fn)
     return out
 
 

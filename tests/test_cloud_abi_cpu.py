@@ -93,8 +93,9 @@ def test_python_interface_refuses_host_tensors_without_a_gpu(built):
     from camradepth_amd import cloud
     K = torch.eye(3, dtype=torch.float64)
     for fn in (cloud.unproject_depth, cloud.point_cloud):
-        with pytest.raises(built.CrdError, match="cuda"):
+        with pytest.raises(built.CrdError, match="cuda") as refusal:
             fn(torch.zeros(1, 416, 800), K)
+        assert "radar" not in str(refusal.value)
         with pytest.raises(built.CrdError, match="encoding"):
             fn(torch.zeros(1, 416, 800), K, encoding="disparity")
     with pytest.raises(built.CrdError, match="stride"):

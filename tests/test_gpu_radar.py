@@ -68,6 +68,11 @@ def raster_points(n, h, w, seed):
         k = ("x1", "y1", "depth1", "x2", "y2", "v_comp", "depth1", "depth1")[i % 8]
         p[k][i] = (np.nan, np.inf, -np.inf, 0.0, -1.0)[(i // 8) % 5] if k == "depth1" else (np.nan, np.inf, -np.inf)[(i // 8) % 3]
     p["valid"] = (rs.uniform(size=n) < 0.9).astype(np.uint8)
+    good = np.nonzero(spot & ~bad & (p["valid"] == 1))[0]                            # on the pixel of a good point and nearer than any,
+    j = good[good + 1 < n][0]                                                        # one that only a non-finite v_comp keeps out
+    for k in ("x1", "y1", "x2", "y2"):
+        p[k][j + 1] = p[k][j]
+    p["depth1"][j + 1], p["v_comp"][j + 1], p["valid"][j + 1] = 0.5 * depths.min(), np.nan, 1
     return p
 
 
@@ -101,6 +106,22 @@ def test_fixture_of_the_reference_rasteriser(radar, golden_dir):
     assert_equal(got_vel, want_vel, "rad_vel")
 
 
+def v_comp_only_point(proj, off, size, s, cut, candidates):
+    """The first point that the rasteriser skips for its v_comp alone (every other value is finite, depth1 > 0, valid, below the
+    cutoff) and that is nearer than every candidate of its pixel, of which there is one at least; or None."""
+    h_new, w_new = size[0] // s, size[1] // s
+    with np.errstate(invalid="ignore"):
+        frame = np.searchsorted(off, np.arange(len(proj["x1"])), side="right")
+        pixel = (frame * h_new + np.rint(ref.scaled(proj["y1"], s, h_new - 1))) * w_new + np.rint(ref.scaled(proj["x1"], s, w_new - 1))
+        rest = np.stack([np.asarray(proj[k]) for k in ref.PROJ_KEYS if k != "v_comp"])
+        alone = ~np.isfinite(proj["v_comp"]) & np.isfinite(rest).all(axis=0) & (proj["depth1"] > 0) & (proj["valid"] == 1) & \
+            (np.rint(ref.scaled(proj["y1"], s, h_new - 1)) >= cut)
+    nearest = {}
+    for j in np.nonzero(candidates)[0]:
+        nearest[pixel[j]] = min(proj["depth1"][j], nearest.get(pixel[j], np.inf))
+    return next((int(i) for i in np.nonzero(alone)[0] if proj["depth1"][i] < nearest.get(pixel[i], -np.inf)), None)
+
+
 CASES = {
     "ragged": dict(size=(128, 192), s=2, cut=4, counts=(0, 1, 600, 37), per_frame_K=False),
     "integer_division": dict(size=(101, 150), s=2, cut=0, counts=(300, 80), per_frame_K=False),
@@ -129,6 +150,13 @@ def test_ragged_batches_against_the_restatement(radar, name):
         candidates = (proj["valid"] == 1) & np.isfinite(arrs).all(axis=0) & (proj["depth1"] > 0) & \
                      (np.rint(ref.scaled(proj["y1"], c["s"], h // c["s"] - 1)) >= c["cut"])
     assert all((k == 0) == (m == 0) for k, m in zip(won, c["counts"])) and sum(won) <= candidates.sum() - 10      # pixels are fought over
+    # a point that only its v_comp keeps out, on a pixel that is fought over: without it the maps are the same, with a finite v_comp not
+    i = v_comp_only_point(proj, off, c["size"], c["s"], c["cut"], candidates)
+    assert i is not None
+    without = ref.rasterize({k: np.delete(np.asarray(v), i) for k, v in proj.items()}, off - (off > i), K, c["size"], c["s"], c["cut"])
+    finite = ref.rasterize(dict(proj, v_comp=np.where(np.arange(n) == i, 0.9, proj["v_comp"])), off, K, c["size"], c["s"], c["cut"])
+    assert np.array_equal(without[0], want_radar) and np.array_equal(without[1], want_vel)
+    assert not (np.array_equal(finite[0], want_radar) and np.array_equal(finite[1], want_vel))
     got_radar, got_vel = run_raster(radar, proj, off, K, c["size"], c["s"], c["cut"])
     assert_equal(got_radar, want_radar, "radar")
     assert_equal(got_vel, want_vel, "rad_vel")

@@ -267,9 +267,13 @@ def test_python_interface_refuses_host_tensors_without_a_gpu(built):
     proj = dict({k: z for k in lidar.PROJ_KEYS}, low_h=u, in_box=u)
     with pytest.raises(built.CrdError, match="cuda"):
         lidar.lidar_ground_truth(proj, torch.tensor([0, 4], dtype=torch.int32), torch.eye(3, dtype=torch.float64))
-    with pytest.raises(built.CrdError, match="cuda"):
+    with pytest.raises(built.CrdError, match="cuda") as refusal:
         lidar.project_lidar(torch.zeros(4, 3, dtype=torch.float64), torch.zeros(4, dtype=torch.int32), torch.tensor([0, 4], dtype=torch.int32),
                             torch.zeros(1, 3, 4, dtype=torch.float64), torch.zeros(1, 3, 4, dtype=torch.float64),
                             torch.zeros(1, 4, dtype=torch.float64), torch.eye(3, dtype=torch.float64))
+    assert "radar" not in str(refusal.value)
+    with pytest.raises(built.CrdError, match="leave no pixel") as refusal:              # a bad map size
+        lidar.lidar_ground_truth(proj, torch.tensor([0, 4], dtype=torch.int32), torch.eye(3, dtype=torch.float64), y_cutoff=450)
+    assert "radar" not in str(refusal.value)
     assert lidar.map_shape((900, 1600), 2, 34) == (416, 800)
     assert lidar.workspace_bytes(3) == 16 + 24 + 8 and lidar.workspace_bytes(4, 2) == 16 + 32 + 64

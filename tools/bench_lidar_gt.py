@@ -3,7 +3,7 @@
 900 x 1600 -> 416 x 800, both occlusion filters on.  Warm runs, device events, the median; one JSON line.
 
     python tools/bench_lidar_gt.py --runs 30
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_lidar_gt.py --runs 20        # the per-launch split (k_lidar_*)
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_lidar_gt.py --runs 20        # the per-launch split (k_lidar_*, k_zbuf_*)
 """
 import argparse
 import json
