@@ -806,6 +806,68 @@ int crd_point_cloud(const float* depth, int32_t B, int32_t im_h, int32_t im_w, i
                     int32_t* frame_offsets, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
+ * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
+ * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
+ * signature: CRD_ABI_VERSION stays.  tests/viz_ref.py restates the arithmetic in NumPy; the kernels agree with it bit for bit.
+ *
+ * A map is fp32 [B][h][w] (kind CRD_VIZ_FLOAT) or uint8 [B][h][w] (kind CRD_VIZ_LABELS).  Its colour is a row of table, uint8
+ * [256][3] (R, G, B) on the device.  With (vmin, vmax) the frame's range, both fp32:
+ *   float map: the map and the scaling are fp32, the range is held in fp64 -- matplotlib 3.10 keeps vmin / vmax as Python floats and
+ *   NumPy 2 then takes the fp64 loop for `fp32 array -= fp64 scalar` and `/=`, rounding each result into the fp32 array:
+ *     t = (float)((double)x - (double)vmin);  q = (float)((double)t / ((double)vmax - (double)vmin));  y = q * 256   (fp32)
+ *   labels, all in fp64 (matplotlib promotes integer input):  y = ((double)l - vmin) / ((double)vmax - vmin) * 256
+ *   row = 255 where y >= 256 (so x == vmax is the last row), trunc(y) where 0 <= y < 256, 0 otherwise (y < 0 and NaN);
+ *   vmin == vmax: row 0 for every pixel.  This is what matplotlib's plt.imsave(cmap=) writes, alpha dropped.
+ * A non-finite pixel of a float map is left out of the range and drawn in bad_rgb (matplotlib turns the whole frame "bad").
+ *
+ * There are three entries where the per-frame range, the drawing and the arg-max make three kinds of launch.  crd_seg_argmax above is
+ * Seg_Block's normalised arg-max into a pixel-major channel; the label map the pictures and crd_point_cloud take is crd_seg_labels.
+ * ------------------------------------------------------------------------------------------- */
+#define CRD_VIZ_TILE 1024      /* pixels of one frame per workgroup of the range pass and per workspace entry */
+#define CRD_VIZ_FLOAT 0
+#define CRD_VIZ_LABELS 1
+#define CRD_VIZ_NONE 0         /* out = colour */
+#define CRD_VIZ_PASTE 1        /* out = colour where x > 0 (l > 0), the image elsewhere            visualization.py:108,141 */
+#define CRD_VIZ_BLEND 2        /* out = clamp(rint(img * alpha + colour * beta), 0, 255)            visualization.py:150 */
+#define CRD_VIZ_IMAGE 3        /* out = the image in R, G, B order (grey applies); src, table and the range are not read */
+/* range[b] = (vmin, vmax), fp32 [B][2]: the smallest and the largest finite value of frame b, (0, 0) when it has none; labels are
+ * converted to fp32 (exact).  The same bits every run: minimum and maximum of monotone integer keys, per tile of CRD_VIZ_TILE pixels
+ * of one frame into the workspace, then folded by one workgroup per frame; no atomic, no workgroup waits for another.
+ * dilate = 0: the range of src itself.  dilate = k, odd, 1 <= k <= 9 (float maps only): src is the normalised radar depth r (input
+ * channel 3); t = 1 - r where r != 0 and r is finite, else 0 (visualization.py:135); dilated[b][r][c] = the maximum of t over the part
+ * of the k x k window around (r, c) that lies inside the frame (cv2.dilate's default border, visualization.py:137); dilated, fp32
+ * [B][h][w], is written in full and the range is that of dilated.
+ * workspace: 8-byte aligned, workspace_bytes >= 8 * B * ceil(h * w / CRD_VIZ_TILE).  A float src, dilated and range are 4-byte aligned;
+ * 16-byte aligned maps of a multiple of four pixels per frame take the vector loads.
+ * CRD_E_INVALID: a NULL src, workspace or range (or dilated with dilate != 0); B, h or w <= 0; kind not 0 or 1; dilate even, negative,
+ * above 9 or given with labels; a workspace too small; misaligned pointers.  CRD_E_UNSUPPORTED: h * w or the number of tiles beyond the
+ * 32-bit indices. */
+int crd_viz_range(const void* src, int32_t kind, int32_t B, int32_t h, int32_t w, int32_t dilate, float* dilated, void* workspace,
+                  int64_t workspace_bytes, float* range, crd_stream_t stream);
+/* The one drawing launch: out[b][r][c] = 3 bytes R, G, B at out + b * out_frame_pitch + r * out_row_pitch + 3 * c (pitches in bytes), so
+ * out may be a panel of a larger canvas; bytes outside the h x 3w rectangles are not touched.
+ * range: fp32 [B][2] on the device (crd_viz_range's, or the caller's own, e.g. smoothed over time), or NULL: every frame takes vmin and
+ * vmax (finite, vmin <= vmax).  bad_rgb: R | G << 8 | B << 16.
+ * image: uint8 [B][h][w][3], the layout of crd_assemble_input, in B, G, R order (image_bgr != 0, "as cv2 reads it") or R, G, B; NULL
+ * with CRD_VIZ_NONE.  grey != 0: the image is first replaced by (R * 9798 + G * 19235 + B * 3735 + 16384) >> 15 in all three channels
+ * (visualization.py:131-132; the 15-bit fixed point of 0.299 / 0.587 / 0.114).  CRD_VIZ_BLEND, per channel in fp32, each operation
+ * rounded on its own: t = img * alpha, u = colour * beta, s = t + u, then round half to even and clamp to 0 .. 255 (|alpha|, |beta| <=
+ * 1e30).  Blend and grey are this definition; they are not pinned to OpenCV's.
+ * Map, image and table are read once; four pixels make three dword stores when w is a multiple of 4, src is 16-byte (labels: 4-byte)
+ * aligned and image, out and both pitches are multiples of 4, byte stores otherwise.
+ * CRD_E_INVALID: NULL out, src or table (unless CRD_VIZ_IMAGE), image (unless CRD_VIZ_NONE); B, h or w <= 0; kind or mode out of range;
+ * out_row_pitch < 3 * w; B > 1 and out_frame_pitch < (h - 1) * out_row_pitch + 3 * w; without range vmin or vmax not finite or vmax <
+ * vmin; alpha or beta out of range; bad_rgb outside 24 bits; a misaligned range or float map.  CRD_E_UNSUPPORTED as above. */
+int crd_viz_draw(const void* src, int32_t kind, int32_t B, int32_t h, int32_t w, const uint8_t* table, const float* range, float vmin,
+                 float vmax, int32_t bad_rgb, const uint8_t* image, int32_t image_bgr, int32_t mode, float alpha, float beta,
+                 int32_t grey, uint8_t* out, int64_t out_row_pitch, int64_t out_frame_pitch, crd_stream_t stream);
+/* labels[b][r][c] = the first index of the maximum of logits[b][.][r][c] (fp32 [B][C][h][w], 1 <= C <= 256; labels uint8 [B][h][w]); a
+ * NaN counts as larger than everything and the first NaN wins: np.argmax(axis=1), torch.max(dim=1)[1] (visualization.py:120).
+ * CRD_E_INVALID: NULL pointers, B, h or w <= 0, C outside 1 .. 256, logits not 4-byte aligned. */
+int crd_seg_labels(const float* logits, int32_t B, int32_t C, int32_t h, int32_t w, uint8_t* labels, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Losses (src/utils/loss_funcs.py:14-46,77-91; combination src/main/runner.py:197-218).
  * ------------------------------------------------------------------------------------------- */
 /* acc[0] += sum smooth_l1(pred-target), acc[1] += #(target>0), acc[2] += sum (target-pred)^2 ; crd_sum_t with
