@@ -239,6 +239,23 @@ __device__ __forceinline__ void grad_add(crd_sum_t* p, float v) { fx_add(p, to_f
 __device__ __forceinline__ float stat_get(const crd_sum_t* p) { return (float)(*p) * (1.f / STAT_ONE); }
 __device__ __forceinline__ float grad_get(const crd_sum_t* p) { return (float)(*p) * (1.f / GRAD_ONE); }
 
+// Workgroup sums of up to three per-thread partials -> crd_sum_t accumulators (NULL: not summed), for workgroups of 256 threads:
+// a butterfly per wave, the four wave sums added in a fixed order, one fixed-point atomic per sum from thread 0 -- the total does
+// not depend on the order of the workgroups, so a loss value and its gradient scale reproduce.  One call per kernel (no barrier
+// behind the LDS reads).
+__device__ __forceinline__ void block_stat_add3(float a, float b, float c, crd_sum_t* pa, crd_sum_t* pb, crd_sum_t* pc) {
+  a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
+  __shared__ float sm[3][4];
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (l == 0) { sm[0][w] = a; sm[1][w] = b; sm[2][w] = c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (pa) stat_add(pa, sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3]);
+    if (pb) stat_add(pb, sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3]);
+    if (pc) stat_add(pc, sm[2][0] + sm[2][1] + sm[2][2] + sm[2][3]);
+  }
+}
+
 // mean / rstd of GroupNorm group from g16 slab sums: group = gmul consecutive slabs starting at slab0
 // mean and 1/sqrt(var + eps) of `count` elements from their fixed-point sums.  E[x^2] - mean^2 in fp64: in fp32 the difference
 // loses mean^2 / var of its 24 bits (groups whose mean is 30x their deviation kept 14), fp64 keeps what the integer sums hold.
@@ -311,3 +328,10 @@ namespace { struct CrdNonfiniteRegistrar { CrdNonfiniteRegistrar() { crd_registe
 
 static inline hipStream_t as_stream(crd_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride kernel: one workgroup per tpb items, at least one and at most cap (the kernel loops over the rest)
+static inline int blocks_for(long long total, int tpb, int cap) {
+  long long n = (total + tpb - 1) / tpb;
+  if (n > cap) n = cap;
+  if (n < 1) n = 1;
+  return (int)n;
+}

@@ -259,19 +259,12 @@ __global__ __launch_bounds__(TPB) void k_augment_gather(const T* src, T* dst, T*
   }
 }
 
-inline int blocks_for(long long total, int cap = 1024) {
-  long long n = (total + TPB - 1) / TPB;
-  if (n > cap) n = cap;
-  if (n < 1) n = 1;
-  return (int)n;
-}
-
 // successive min-pool levels of `src` [B][h][w], down to the first NULL
 void launch_minpool_levels(const float* src, int B, int h, int w, float* half, float* quarter, float* eighth, hipStream_t st) {
   float* lv[3] = {half, quarter, eighth};
   for (int i = 0; i < 3 && lv[i]; ++i) {
     const int oh = (h + 2 - 3) / 2 + 1, ow = (w + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(k_gt_minpool, dim3(blocks_for((long long)oh * ow, 256), B), dim3(TPB), 0, st, src, h, w, lv[i]);
+    hipLaunchKernelGGL(k_gt_minpool, dim3(blocks_for((long long)oh * ow, TPB, 256), B), dim3(TPB), 0, st, src, h, w, lv[i]);
     src = lv[i]; h = oh; w = ow;
   }
 }
@@ -282,7 +275,7 @@ extern "C" int crd_assemble_input(const void* img_u8, const float* radar, const 
                                   float max_depth, float* out, crd_stream_t stream) {
   CRD_CHECK_ARG(img_u8 && radar && out && B > 0 && H > 0 && W > 0 && max_depth > 0.f, "crd_assemble_input: bad argument");
   const long long HW = (long long)H * W;
-  hipLaunchKernelGGL(k_assemble_input, dim3(blocks_for(HW), B), dim3(TPB), 0, as_stream(stream),
+  hipLaunchKernelGGL(k_assemble_input, dim3(blocks_for(HW, TPB, 1024), B), dim3(TPB), 0, as_stream(stream),
                      reinterpret_cast<const unsigned char*>(img_u8), radar, rad_vel, HW, max_depth, rad_vel ? 7 : 6, out);
   CRD_LAUNCH_CHECK("crd_assemble_input");
   return CRD_OK;
@@ -293,7 +286,7 @@ extern "C" int crd_gt_pyramid(const float* depth, int32_t B, int32_t H, int32_t 
   CRD_CHECK_ARG(depth && full && B > 0 && H > 0 && W > 0 && max_depth > 0.f, "crd_gt_pyramid: bad argument");
   CRD_CHECK_ARG(!(quarter && !half) && !(eighth && !quarter), "crd_gt_pyramid: a level needs the one above it");
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(k_gt_inverse, dim3(blocks_for((long long)B * H * W)), dim3(TPB), 0, st, depth, (long long)B * H * W, max_depth, full);
+  hipLaunchKernelGGL(k_gt_inverse, dim3(blocks_for((long long)B * H * W, TPB, 1024)), dim3(TPB), 0, st, depth, (long long)B * H * W, max_depth, full);
   launch_minpool_levels(full, B, H, W, half, quarter, eighth, st);
   CRD_LAUNCH_CHECK("crd_gt_pyramid");
   return CRD_OK;
@@ -302,7 +295,7 @@ extern "C" int crd_gt_pyramid(const float* depth, int32_t B, int32_t H, int32_t 
 extern "C" int crd_resize_nearest_u8(const void* src, int32_t B, int32_t SH, int32_t SW, int32_t C, void* dst, int32_t DH, int32_t DW,
                                      crd_stream_t stream) {
   CRD_CHECK_ARG(src && dst && B > 0 && SH > 0 && SW > 0 && C > 0 && DH > 0 && DW > 0, "crd_resize_nearest_u8: bad argument");
-  hipLaunchKernelGGL(k_resize_nearest_u8, dim3(blocks_for((long long)DH * DW), B), dim3(TPB), 0, as_stream(stream),
+  hipLaunchKernelGGL(k_resize_nearest_u8, dim3(blocks_for((long long)DH * DW, TPB, 1024), B), dim3(TPB), 0, as_stream(stream),
                      reinterpret_cast<const unsigned char*>(src), SH, SW, C, reinterpret_cast<unsigned char*>(dst), DH, DW);
   CRD_LAUNCH_CHECK("crd_resize_nearest_u8");
   return CRD_OK;
@@ -311,7 +304,7 @@ extern "C" int crd_resize_nearest_u8(const void* src, int32_t B, int32_t SH, int
 extern "C" int crd_resize_labels_nearest(const void* src_u8, int32_t B, int32_t SH, int32_t SW, int32_t rows, int64_t* dst, int32_t DH,
                                          int32_t DW, crd_stream_t stream) {
   CRD_CHECK_ARG(src_u8 && dst && B > 0 && SH > 0 && SW > 0 && rows > 0 && DH > 0 && DW > 0, "crd_resize_labels_nearest: bad argument");
-  hipLaunchKernelGGL(k_resize_labels, dim3(blocks_for((long long)DH * DW), B), dim3(TPB), 0, as_stream(stream),
+  hipLaunchKernelGGL(k_resize_labels, dim3(blocks_for((long long)DH * DW, TPB, 1024), B), dim3(TPB), 0, as_stream(stream),
                      reinterpret_cast<const unsigned char*>(src_u8), SH, rows < SH ? rows : SH, SW, reinterpret_cast<long long*>(dst), DH, DW);
   CRD_LAUNCH_CHECK("crd_resize_labels_nearest");
   return CRD_OK;
@@ -341,7 +334,7 @@ extern "C" int crd_augment_draw(int32_t* params, float* lut, int32_t B, int32_t 
   CRD_CHECK_ARG(!(enable & CRD_AUGMENT_COLOUR) || (colour_lo >= 0.f && colour_lo <= colour_hi && colour_hi < INFINITY),
                 "crd_augment_draw: bad colour range (%g, %g): 0 <= lo <= hi", (double)colour_lo, (double)colour_hi);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(k_augment_draw, dim3(blocks_for((long long)B * AUG_WORDS)), dim3(TPB), 0, st, params, B, H - h + 1, W - w + 1, p_flip,
+  hipLaunchKernelGGL(k_augment_draw, dim3(blocks_for((long long)B * AUG_WORDS, TPB, 1024)), dim3(TPB), 0, st, params, B, H - h + 1, W - w + 1, p_flip,
                      gamma_lo, gamma_hi, brightness_lo, brightness_hi, colour_lo, colour_hi, enable,
                      (unsigned long long)(seed ^ CRD_AUGMENT_STREAM), (unsigned long long)counter);
   if (lut) hipLaunchKernelGGL(k_augment_lut, dim3(B), dim3(256), 0, st, params, enable, lut);
@@ -372,9 +365,9 @@ extern "C" int crd_augment_assemble(const void* img_u8, const float* radar, cons
   a.fseg = reinterpret_cast<long long*>(final_seg); a.iseg = reinterpret_cast<long long*>(inter_seg);
   a.H = H; a.W = W; a.h = h; a.w = w; a.channels = rad_vel ? 7 : 6; a.max_depth = max_depth;
   if (w % 4 == 0)
-    hipLaunchKernelGGL(k_augment_assemble<4>, dim3(blocks_for((long long)h * (w / 4)), B), dim3(TPB), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_augment_assemble<4>, dim3(blocks_for((long long)h * (w / 4), TPB, 1024), B), dim3(TPB), 0, as_stream(stream), a);
   else
-    hipLaunchKernelGGL(k_augment_assemble<1>, dim3(blocks_for((long long)h * w), B), dim3(TPB), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(k_augment_assemble<1>, dim3(blocks_for((long long)h * w, TPB, 1024), B), dim3(TPB), 0, as_stream(stream), a);
   CRD_LAUNCH_CHECK("crd_augment_assemble");
   return CRD_OK;
 }
@@ -383,10 +376,10 @@ template <typename T>
 static void launch_augment_gather(const T* src, T* dst, T* half, const int32_t* params, int B, int planes, int H, int W, int h, int w,
                                   int neg_plane, hipStream_t st) {
   if (w % 4 == 0)
-    hipLaunchKernelGGL((k_augment_gather<4, T>), dim3(blocks_for((long long)h * (w / 4)), B * planes), dim3(TPB), 0, st, src, dst, half,
+    hipLaunchKernelGGL((k_augment_gather<4, T>), dim3(blocks_for((long long)h * (w / 4), TPB, 1024), B * planes), dim3(TPB), 0, st, src, dst, half,
                        params, planes, H, W, h, w, neg_plane);
   else
-    hipLaunchKernelGGL((k_augment_gather<1, T>), dim3(blocks_for((long long)h * w), B * planes), dim3(TPB), 0, st, src, dst, half, params,
+    hipLaunchKernelGGL((k_augment_gather<1, T>), dim3(blocks_for((long long)h * w, TPB, 1024), B * planes), dim3(TPB), 0, st, src, dst, half, params,
                        planes, H, W, h, w, neg_plane);
 }
 

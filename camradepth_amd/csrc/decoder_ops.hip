@@ -552,13 +552,6 @@ inline int head2_blocks(int H, int W, int B) {
   return (int)(n > cap ? cap : n);
 }
 
-inline int blocks_for(long long total) {
-  long long n = (total + TPB - 1) / TPB;
-  if (n > 4096) n = 4096;
-  if (n < 1) n = 1;
-  return (int)n;
-}
-
 }  // namespace
 
 extern "C" int crd_bicubic2x(const void* x, int32_t x_ld, int32_t x_coff, int32_t B, int32_t H, int32_t W, int32_t C, void* y,
@@ -615,7 +608,7 @@ extern "C" int crd_nchw_to_pm(const float* x, int32_t B, int32_t C, int32_t H, i
   CRD_CHECK_ARG(x && y, "crd_nchw_to_pm: null pointer");
   CRD_CHECK_ARG(Cpad % 8 == 0 && Cpad >= C && y_ld % 8 == 0 && y_coff % 8 == 0, "crd_nchw_to_pm: alignment");
   const long long HW = (long long)H * W;
-  hipLaunchKernelGGL(k_nchw_to_pm, dim3(blocks_for(HW * (Cpad / 8)), B), dim3(TPB), 0, as_stream(stream), x, C, HW,
+  hipLaunchKernelGGL(k_nchw_to_pm, dim3(blocks_for(HW * (Cpad / 8), TPB, 4096), B), dim3(TPB), 0, as_stream(stream), x, C, HW,
                      reinterpret_cast<bf16_t*>(y) + y_coff, y_ld, Cpad);
   CRD_LAUNCH_CHECK("crd_nchw_to_pm");
   return CRD_OK;
@@ -626,7 +619,7 @@ extern "C" int crd_pm_to_nchw(const void* x, int32_t x_f32, int32_t x_ld, int32_
   CRD_CHECK_ARG(x && y, "crd_pm_to_nchw: null pointer");
   const long long HW = (long long)H * W;
   const void* xp = x_f32 ? (const void*)(reinterpret_cast<const float*>(x) + x_coff) : (const void*)(reinterpret_cast<const bf16_t*>(x) + x_coff);
-  hipLaunchKernelGGL(k_pm_to_nchw, dim3(blocks_for(HW * C), B), dim3(TPB), 0, as_stream(stream), xp, x_f32, x_ld, C, HW, y);
+  hipLaunchKernelGGL(k_pm_to_nchw, dim3(blocks_for(HW * C, TPB, 4096), B), dim3(TPB), 0, as_stream(stream), xp, x_f32, x_ld, C, HW, y);
   CRD_LAUNCH_CHECK("crd_pm_to_nchw");
   return CRD_OK;
 }
@@ -636,7 +629,7 @@ extern "C" int crd_seg_argmax(const void* logits, int32_t ld, int32_t B, int32_t
   CRD_CHECK_ARG(logits && y && C >= 1 && num_classes >= 1, "crd_seg_argmax: bad argument");
   const long long rows = (long long)B * P;
   void* yp = y_f32 ? (void*)(reinterpret_cast<float*>(y) + y_coff) : (void*)(reinterpret_cast<bf16_t*>(y) + y_coff);
-  hipLaunchKernelGGL(k_seg_argmax, dim3(blocks_for(rows)), dim3(TPB), 0, as_stream(stream), reinterpret_cast<const float*>(logits),
+  hipLaunchKernelGGL(k_seg_argmax, dim3(blocks_for(rows, TPB, 4096)), dim3(TPB), 0, as_stream(stream), reinterpret_cast<const float*>(logits),
                      ld, rows, C, num_classes, yp, y_f32, y_ld);
   CRD_LAUNCH_CHECK("crd_seg_argmax");
   return CRD_OK;
@@ -644,7 +637,7 @@ extern "C" int crd_seg_argmax(const void* logits, int32_t ld, int32_t B, int32_t
 
 extern "C" int crd_scale_f32(const float* src, float* dst, int64_t n, float scale, crd_stream_t stream) {
   CRD_CHECK_ARG(src && dst && n > 0, "crd_scale_f32: bad argument");
-  hipLaunchKernelGGL(k_scale_f32, dim3(blocks_for(n)), dim3(TPB), 0, as_stream(stream), src, dst, (long long)n, scale);
+  hipLaunchKernelGGL(k_scale_f32, dim3(blocks_for(n, TPB, 4096)), dim3(TPB), 0, as_stream(stream), src, dst, (long long)n, scale);
   CRD_LAUNCH_CHECK("crd_scale_f32");
   return CRD_OK;
 }
@@ -653,7 +646,7 @@ extern "C" int crd_slice_copy(const void* src, int32_t s_ld, int32_t s_coff, voi
                               int64_t rows, int32_t C, int32_t accumulate, crd_stream_t stream) {
   CRD_CHECK_ARG(src && dst, "crd_slice_copy: null pointer");
   CRD_CHECK_ARG(C % 8 == 0 && s_ld % 8 == 0 && s_coff % 8 == 0 && d_ld % 8 == 0 && d_coff % 8 == 0, "crd_slice_copy: alignment");
-  hipLaunchKernelGGL(k_slice_copy, dim3(blocks_for(rows * (C / 8))), dim3(TPB), 0, as_stream(stream),
+  hipLaunchKernelGGL(k_slice_copy, dim3(blocks_for(rows * (C / 8), TPB, 4096)), dim3(TPB), 0, as_stream(stream),
                      reinterpret_cast<const bf16_t*>(src) + s_coff, s_ld, reinterpret_cast<bf16_t*>(dst) + d_coff, d_ld,
                      (long long)rows, C, accumulate);
   CRD_LAUNCH_CHECK("crd_slice_copy");
@@ -666,7 +659,7 @@ extern "C" int crd_f32_to_bf16_rows(const float* src, int32_t s_ld, void* dst, i
   CRD_CHECK_ARG(src && dst && rows_per_sample > 0, "crd_f32_to_bf16_rows: bad argument");
   const int vec = (C % 8 == 0) && (s_ld % 8 == 0) && (d_ld % 8 == 0) && (d_coff % 8 == 0) &&
                   (!add || (add_ld % 8 == 0 && add_coff % 8 == 0)) && ((reinterpret_cast<uintptr_t>(src) & 31) == 0);
-  hipLaunchKernelGGL(k_f32_to_bf16_rows, dim3(blocks_for(vec ? rows * (C / 8) : rows * C)), dim3(TPB), 0, as_stream(stream), src,
+  hipLaunchKernelGGL(k_f32_to_bf16_rows, dim3(blocks_for(vec ? rows * (C / 8) : rows * C, TPB, 4096)), dim3(TPB), 0, as_stream(stream), src,
                      s_ld, reinterpret_cast<bf16_t*>(dst) + d_coff, d_ld, (long long)rows, C, scale, (long long)rows_per_sample,
                      add ? reinterpret_cast<const bf16_t*>(add) + add_coff : nullptr, add_ld, vec);
   CRD_LAUNCH_CHECK("crd_f32_to_bf16_rows");
@@ -724,7 +717,7 @@ extern "C" int crd_head_conv2_wgrad(const float* gd, const void* add, int32_t ad
 
 extern "C" int crd_sigmoid_bwd(const void* a, void* da, int64_t n, crd_stream_t stream) {
   CRD_CHECK_ARG(a && da && n % 8 == 0, "crd_sigmoid_bwd: bad argument");
-  hipLaunchKernelGGL(k_sigmoid_bwd, dim3(blocks_for(n / 8)), dim3(TPB), 0, as_stream(stream), reinterpret_cast<const bf16_t*>(a),
+  hipLaunchKernelGGL(k_sigmoid_bwd, dim3(blocks_for(n / 8, TPB, 4096)), dim3(TPB), 0, as_stream(stream), reinterpret_cast<const bf16_t*>(a),
                      reinterpret_cast<bf16_t*>(da), (long long)(n / 8));
   CRD_LAUNCH_CHECK("crd_sigmoid_bwd");
   return CRD_OK;

@@ -1,14 +1,99 @@
-// Evaluation kernels for gfx950: the standard depth-evaluation sums, binned by true distance (include/camradepth_hip.h:
-// crd_depth_eval).  One HBM-bound pass over prediction and ground truth serves every distance cap and every metric.
+// Evaluation kernels for gfx950: the metrics of Trainer.test (crd_test_metrics, crd_seg_confusion) and the standard
+// depth-evaluation sums, binned by true distance (include/camradepth_hip.h: crd_depth_eval), where one HBM-bound pass over
+// prediction and ground truth serves every distance cap and every metric.
 #include <math.h>
 #include "common.h"
-
-// The per-pixel arithmetic is part of the contract (every statement rounded on its own in fp32): no fused multiply-adds here.
-#pragma clang fp contract(off)
 
 namespace {
 
 constexpr int TPB = 256;
+
+// The metrics of Trainer.test.  They stay ABOVE the fp contract(off) pragma below: they are compiled with the default contraction
+// (sq += e * e is one FMA), as they always were, and crd_test_metrics' sums keep their bits that way.
+
+// Trainer.test metrics (runner.py:443-465), per frame f: pred clipped to [0,1] and both scaled by max_depth, ground truth
+// beyond max_distance dropped; acc[f] = (sum |e|, sum e^2, sum |e|/gt, count)
+__global__ __launch_bounds__(TPB) void k_test_metrics(const float* pred, const float* gt, long long n, float max_depth,
+                                                      float max_distance, crd_sum_t* acc) {
+  const int f = blockIdx.y;
+  const float* p = pred + (long long)f * n;
+  const float* g = gt + (long long)f * n;
+  float sa = 0.f, sq = 0.f, sr = 0.f, cnt = 0.f;
+  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
+    float t = g[i] * max_depth;
+    if (t > max_distance) t = 0.f;
+    if (t > 0.f) {
+      const float e = fminf(fmaxf(p[i], 0.f), 1.f) * max_depth - t;
+      sa += fabsf(e); sq += e * e; sr += fabsf(e) / t; cnt += 1.f;
+    }
+  }
+  sa = wave_sum(sa); sq = wave_sum(sq); sr = wave_sum(sr); cnt = wave_sum(cnt);
+  __shared__ float sm[TPB / 64][4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sm[wave][0] = sa; sm[wave][1] = sq; sm[wave][2] = sr; sm[wave][3] = cnt; }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    float v = 0.f;
+    for (int w = 0; w < TPB / 64; ++w) v += sm[w][threadIdx.x];
+    stat_add(&acc[f * 4 + threadIdx.x], v);
+  }
+}
+
+// Confusion matrix of one frame for the Jaccard index of Trainer.test (runner.py:432-436): prediction = arg-max over the C
+// logits of a pixel (NCHW fp32, first maximal class), confmat[f][target][pred] += 1; labels outside [0, C) are counted in
+// oor[f] and skipped (torchmetrics 0.10.2 raises on them, which the reference catches: that frame's IoU stays NaN).
+__global__ __launch_bounds__(TPB) void k_seg_confusion(const float* logits, const long long* labels, int C, long long HW,
+                                                       unsigned long long* confmat, unsigned long long* oor) {
+  extern __shared__ unsigned int hist[];      // C * C + 1
+  const int f = blockIdx.y;
+  for (int i = threadIdx.x; i <= C * C; i += TPB) hist[i] = 0;
+  __syncthreads();
+  const float* lg = logits + (long long)f * C * HW;
+  const long long* lb = labels + (long long)f * HW;
+  for (long long p = (long long)blockIdx.x * TPB + threadIdx.x; p < HW; p += (long long)gridDim.x * TPB) {
+    const long long t = lb[p];
+    if (t < 0 || t >= C) { atomicAdd(&hist[C * C], 1u); continue; }
+    float best = lg[p];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = lg[(long long)c * HW + p];
+      if (v > best) { best = v; arg = c; }
+    }
+    atomicAdd(&hist[(int)t * C + arg], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < C * C; i += TPB)
+    if (hist[i]) atomicAdd(&confmat[(long long)f * C * C + i], (unsigned long long)hist[i]);
+  if (threadIdx.x == 0 && hist[C * C]) atomicAdd(&oor[f], (unsigned long long)hist[C * C]);
+}
+
+}  // namespace
+
+extern "C" int crd_test_metrics(const float* pred, const float* gt, int32_t frames, int64_t n, float max_depth, float max_distance,
+                                crd_sum_t* acc, crd_stream_t stream) {
+  CRD_CHECK_ARG(pred && gt && acc && frames > 0 && n > 0, "crd_test_metrics: bad argument");
+  hipLaunchKernelGGL(k_test_metrics, dim3(blocks_for(n, TPB, 64), frames), dim3(TPB), 0, as_stream(stream), pred, gt, (long long)n,
+                     max_depth, max_distance, acc);
+  CRD_LAUNCH_CHECK("crd_test_metrics");
+  return CRD_OK;
+}
+
+extern "C" int crd_seg_confusion(const float* logits, const int64_t* labels, int32_t frames, int32_t C, int64_t HW, int64_t* confmat,
+                                 int64_t* out_of_range, crd_stream_t stream) {
+  CRD_CHECK_ARG(logits && labels && confmat && out_of_range && frames > 0 && C > 0 && C <= 64 && HW > 0, "crd_seg_confusion: bad argument");
+  hipLaunchKernelGGL(k_seg_confusion, dim3(blocks_for(HW, TPB, 128), frames), dim3(TPB), (C * C + 1) * sizeof(unsigned int), as_stream(stream),
+                     logits, reinterpret_cast<const long long*>(labels), C, (long long)HW,
+                     reinterpret_cast<unsigned long long*>(confmat), reinterpret_cast<unsigned long long*>(out_of_range));
+  CRD_LAUNCH_CHECK("crd_seg_confusion");
+  return CRD_OK;
+}
+
+// From here on the per-pixel arithmetic is part of the contract (every statement rounded on its own in fp32): no fused
+// multiply-adds.
+#pragma clang fp contract(off)
+
+namespace {
+
 constexpr int PIX_PER_THREAD = 8;                // two 16-byte loads of each input per thread
 constexpr int CHUNK = TPB * PIX_PER_THREAD;      // pixels of one workgroup: a contiguous piece of one frame
 constexpr int COLS = CRD_EVAL_COLUMNS;

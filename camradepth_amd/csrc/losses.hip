@@ -1,8 +1,8 @@
-// Depth criteria beyond the default trainer's smooth-L1 (src/utils/loss_funcs.py:49-59,118-180): masked L1 / RMSE, the reverse
-// Huber (BerHu) and the edge-aware smoothness loss.  Conventions of train_ops.hip's k_masked_l1_fwd / _bwd: flat fp32 pred and
-// target, mask target > 0, every cross-workgroup sum a crd_sum_t (CRD_STAT_FRAC_BITS, bit-reproducible and exact under a SUM
-// all-reduce), no host synchronisation.  MaskedHuberLoss is nn.HuberLoss(delta=1), i.e. smooth-L1 with beta = 1: it runs
-// crd_masked_l1_fwd / _bwd and has no kernel here.  All are HBM-bound streaming kernels.
+// Every loss for gfx950 (src/utils/loss_funcs.py:14-91,118-180): the masked depth criteria -- smooth-L1 / MSE partials, L1 / RMSE,
+// the reverse Huber (BerHu) -- the edge-aware smoothness loss, and cross entropy with its focal backward.  Conventions: flat fp32
+// pred and target, mask target > 0, every cross-workgroup sum a crd_sum_t (CRD_STAT_FRAC_BITS, bit-reproducible and exact under a
+// SUM all-reduce), no host synchronisation.  MaskedHuberLoss is nn.HuberLoss(delta=1), i.e. smooth-L1 with beta = 1: it runs
+// crd_masked_l1_fwd / _bwd and has no kernel of its own.  All are HBM-bound streaming kernels.
 #include <math.h>
 #include <string.h>
 #include "common.h"
@@ -11,84 +11,73 @@ namespace {
 
 constexpr int TPB = 256;
 
-inline int blocks_for(long long total, int cap = 2048) {
-  long long n = (total + TPB - 1) / TPB;
-  if (n > cap) n = cap;
-  if (n < 1) n = 1;
-  return (int)n;
-}
-
-// workgroup sums of up to three partials -> crd_sum_t accumulators (NULL: not summed)
-__device__ __forceinline__ void block_add3(float a, float b, float c, crd_sum_t* pa, crd_sum_t* pb, crd_sum_t* pc) {
-  a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
-  __shared__ float sm[3][TPB / 64];
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (l == 0) { sm[0][w] = a; sm[1][w] = b; sm[2][w] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (pa) stat_add(pa, sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3]);
-    if (pb) stat_add(pb, sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3]);
-    if (pc) stat_add(pc, sm[2][0] + sm[2][1] + sm[2][2] + sm[2][3]);
-  }
-}
-
 __device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }   // torch.sgn: 0 at 0
 
-// MaskedL1Loss / MaskedRMSELoss partials: acc[0] += sum |d|, acc[1] += count, acc[2] += sum d^2   (d = pred - target)
-__global__ __launch_bounds__(TPB) void k_masked_dist_fwd(const float* pred, const float* target, long long n, crd_sum_t* acc) {
+// the depth criteria that share the masked loop of their forward partials and of their backward, d = pred - target
+enum { SMOOTH_L1, DIST, BERHU };
+
+// Forward partials over the mask: acc[1] += count, acc[2] += sum d^2, and
+//   SMOOTH_L1 (MaskedSmoothL1Loss / MaskedMSELoss, loss_funcs.py:40-46, 83-91): acc[0] += sum of 0.5 d^2 if |d| < 1, else |d| - 0.5
+//   DIST (MaskedL1Loss / MaskedRMSELoss): acc[0] += sum |d|
+//   BERHU, phase (a): *maxbits = max |d| (the bit pattern of a non-negative float orders like an unsigned integer, so an integer
+//   atomic max is exact in any order); acc[0] is left alone
+template <int CRIT>
+__global__ __launch_bounds__(TPB) void k_masked_fwd(const float* pred, const float* target, long long n, crd_sum_t* acc,
+                                                    unsigned int* maxbits) {
   float s = 0.f, cnt = 0.f, sq = 0.f;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
-    const float t = target[i];
-    if (t > 0.f) {
-      const float e = pred[i] - t;
-      s += fabsf(e);
-      sq += e * e;
-      cnt += 1.f;
-    }
-  }
-  block_add3(s, cnt, sq, acc, acc + 1, acc + 2);
-}
-
-// mode 0 (L1): g sign(d) / count;  mode 1 (RMSE): g d / (count rmse) -- NaN on the mask when rmse = 0, as torch's sqrt backward
-__global__ __launch_bounds__(TPB) void k_masked_dist_bwd(const float* pred, const float* target, long long n, const crd_sum_t* acc,
-                                                         const float* gout, float gmul, int mode, float* dpred) {
-  const double cnt = (double)acc[1] * (1.0 / STAT_ONE);
-  const double rmse = sqrt((double)acc[2] * (1.0 / STAT_ONE) / cnt);
-  const float g = (float)((double)(gmul * (gout ? gout[0] : 1.f)) / (mode == 0 ? cnt : cnt * rmse));
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
-    const float t = target[i];
-    float d = 0.f;
-    if (t > 0.f) {
-      const float e = pred[i] - t;
-      d = mode == 0 ? g * sgnf(e) : g * e;
-    }
-    dpred[i] = d;
-  }
-}
-
-// BerHu phase (a): max |d| over the mask (the bit pattern of a non-negative float orders like an unsigned integer, so an integer
-// atomic max is exact in any order), acc[1] += count, acc[2] += sum d^2
-__global__ __launch_bounds__(TPB) void k_berhu_max(const float* pred, const float* target, long long n, crd_sum_t* acc,
-                                                   unsigned int* maxbits) {
-  float cnt = 0.f, sq = 0.f;
   unsigned int mx = 0u;
   for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
     const float t = target[i];
     if (t > 0.f) {
       const float e = pred[i] - t;
+      if constexpr (CRIT == SMOOTH_L1) {
+        const float ae = fabsf(e);
+        s += ae < 1.f ? 0.5f * e * e : ae - 0.5f;
+      }
+      if constexpr (CRIT == DIST) s += fabsf(e);
       sq += e * e;
       cnt += 1.f;
-      const unsigned int b = __float_as_uint(fabsf(e));
-      mx = b > mx ? b : mx;
+      if constexpr (CRIT == BERHU) {
+        const unsigned int b = __float_as_uint(fabsf(e));
+        mx = b > mx ? b : mx;
+      }
     }
   }
+  if constexpr (CRIT == BERHU) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned int v = (unsigned int)__shfl_xor((int)mx, o);
-    mx = v > mx ? v : mx;
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned int v = (unsigned int)__shfl_xor((int)mx, o);
+      mx = v > mx ? v : mx;
+    }
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(maxbits, mx);
   }
-  if ((threadIdx.x & 63) == 0 && mx) atomicMax(maxbits, mx);
-  block_add3(0.f, cnt, sq, nullptr, acc + 1, acc + 2);
+  block_stat_add3(s, cnt, sq, CRIT == BERHU ? nullptr : acc, acc + 1, acc + 2);
+}
+
+// Backward of the one-kernel criteria, g = gmul * gout[0] (1 if NULL):
+//   SMOOTH_L1: g clamp(d, -1, 1) / count
+//   DIST, mode 0 (L1): g sign(d) / count;  mode 1 (RMSE): g d / (count rmse) -- NaN on the mask when rmse = 0, as torch's sqrt backward
+template <int CRIT>
+__global__ __launch_bounds__(TPB) void k_masked_bwd(const float* pred, const float* target, long long n, const crd_sum_t* acc,
+                                                    const float* gout, float gmul, int mode, float* dpred) {
+  float g;
+  if constexpr (CRIT == SMOOTH_L1) {
+    g = gmul * (gout ? gout[0] : 1.f) / stat_get(acc + 1);
+  } else {
+    const double cnt = (double)acc[1] * (1.0 / STAT_ONE);
+    const double rmse = sqrt((double)acc[2] * (1.0 / STAT_ONE) / cnt);
+    g = (float)((double)(gmul * (gout ? gout[0] : 1.f)) / (mode == 0 ? cnt : cnt * rmse));
+  }
+  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
+    const float t = target[i];
+    float d = 0.f;
+    if (t > 0.f) {
+      const float e = pred[i] - t;
+      if constexpr (CRIT == SMOOTH_L1) d = g * fminf(fmaxf(e, -1.f), 1.f);
+      else d = mode == 0 ? g * sgnf(e) : g * e;
+    }
+    dpred[i] = d;
+  }
 }
 
 // BerHu phase (b) with c = thresh * (global max |d|) formed in fp64 as the reference's delta, the reference's fp32 edges (F.threshold
@@ -122,7 +111,7 @@ __global__ __launch_bounds__(TPB) void k_berhu(const float* pred, const float* t
     }
     if (dpred) dpred[i] = dp;
   }
-  if (loss) block_add3(s1, s2, 0.f, loss, loss + 1, nullptr);
+  if (loss) block_stat_add3(s1, s2, 0.f, loss, loss + 1, nullptr);
 }
 
 // SmoothnessLoss, per sample b: acc[3b] += sum p
@@ -131,7 +120,7 @@ __global__ __launch_bounds__(TPB) void k_smooth_sum(const float* pred, int HW, c
   const float* p = pred + (long long)b * HW;
   float s = 0.f;
   for (int i = blockIdx.x * TPB + threadIdx.x; i < HW; i += gridDim.x * TPB) s += p[i];
-  block_add3(s, 0.f, 0.f, acc + 3 * b, nullptr, nullptr);
+  block_stat_add3(s, 0.f, 0.f, acc + 3 * b, nullptr, nullptr);
 }
 
 // edge weights exp(-mean_c |I[i] - I[j]|)
@@ -158,7 +147,7 @@ __global__ __launch_bounds__(TPB) void k_smooth_fwd(const float* pred, const flo
     if (w < W - 1) sx += fabsf(n0 - p[i + 1] / den) * edge_weight(img, HW, C, i, i + 1);
     if (h < H - 1) sy += fabsf(n0 - p[i + W] / den) * edge_weight(img, HW, C, i, i + W);
   }
-  block_add3(0.f, sx, sy, nullptr, acc + 3 * b + 1, acc + 3 * b + 2);
+  block_stat_add3(0.f, sx, sy, nullptr, acc + 3 * b + 1, acc + 3 * b + 2);
 }
 
 // dL/dp_k = (dL/dn_k - L_b / HW) / (mean_b + 1e-7): the mean's term needs sum_j dL/dn_j n_j, which is L_b (L is positively
@@ -185,11 +174,84 @@ __global__ __launch_bounds__(TPB) void k_smooth_bwd(const float* pred, const flo
   }
 }
 
+// Cross entropy over NCHW fp32 logits, labels int64 [B][HW], ignore_index 255 (loss_funcs.py:22,27).  Any other label outside
+// [0, C) -- torch raises on it -- never forms an address: the pixel adds nothing to the sum or the count and is counted in acc[2]
+// (as k_seg_confusion counts it in oor[f]); the callers raise on a non-zero count.  acc is nonnull (crd_ce_fwd refuses NULL): the
+// kernel then carries no NULL test for block_stat_add3's first target.
+__global__ __launch_bounds__(TPB) void k_ce_fwd(const float* logits, const long long* labels, int C, long long HW, long long rows,
+                                                crd_sum_t* acc __attribute__((nonnull))) {
+  float s = 0.f, cnt = 0.f, bad = 0.f;
+  for (long long r = (long long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long long)gridDim.x * TPB) {
+    const long long lab = labels[r];
+    if (lab == 255) continue;
+    if (lab < 0 || lab >= C) { bad += 1.f; continue; }
+    const long long b = r / HW, p = r - b * HW;
+    const float* base = logits + (b * C) * HW + p;
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, base[(long long)c * HW]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(base[(long long)c * HW] - mx);
+    // log-sum-exp minus the SHIFTED target logit: (mx + log se) - x[lab] would round at the magnitude of the logits themselves
+    // (5e-4 per pixel for logits near 1e4), x[lab] - mx is small and nearly exact
+    s += logf(se) - (base[lab * HW] - mx);
+    cnt += 1.f;
+  }
+  block_stat_add3(s, cnt, bad, acc, acc + 1, acc + 2);
+}
+
+// focal on the scalar mean CE: F=(1-e^-ce)^2 ce ; dF/dce = 2(1-pt)pt ce + (1-pt)^2
+__global__ __launch_bounds__(TPB) void k_ce_focal_bwd(const float* logits, const long long* labels, int C, long long HW,
+                                                      long long rows, const crd_sum_t* acc, const float* gout, float gmul,
+                                                      float* dlogits) {
+  const float cnt = stat_get(acc + 1);
+  const float ce = stat_get(acc) / cnt;
+  const float pt = expf(-ce);
+  const float dF = 2.f * (1.f - pt) * pt * ce + (1.f - pt) * (1.f - pt);
+  const float g = gmul * (gout ? gout[0] : 1.f) * dF / cnt;
+  for (long long r = (long long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long long)gridDim.x * TPB) {
+    const long long lab = labels[r];
+    const long long b = r / HW, p = r - b * HW;
+    const float* base = logits + (b * C) * HW + p;
+    float* dbase = dlogits + (b * C) * HW + p;
+    if (lab == 255 || lab < 0 || lab >= C) {      // ignored, or out of range (counted by k_ce_fwd): no gradient
+      for (int c = 0; c < C; ++c) dbase[(long long)c * HW] = 0.f;
+      continue;
+    }
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, base[(long long)c * HW]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(base[(long long)c * HW] - mx);
+    const float inv = 1.f / se;
+    for (int c = 0; c < C; ++c) {
+      float sm = expf(base[(long long)c * HW] - mx) * inv;
+      dbase[(long long)c * HW] = g * (sm - (c == lab ? 1.f : 0.f));
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int crd_masked_l1_fwd(const float* pred, const float* target, int64_t n, crd_sum_t* acc, crd_stream_t stream) {
+  CRD_CHECK_ARG(pred && target && acc && n > 0, "crd_masked_l1_fwd: bad argument");
+  hipLaunchKernelGGL(k_masked_fwd<SMOOTH_L1>, dim3(blocks_for(n, TPB, 512)), dim3(TPB), 0, as_stream(stream), pred, target,
+                     (long long)n, acc, (unsigned int*)nullptr);
+  CRD_LAUNCH_CHECK("crd_masked_l1_fwd");
+  return CRD_OK;
+}
+
+extern "C" int crd_masked_l1_bwd(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const float* gout,
+                                 float gmul, float* dpred, crd_stream_t stream) {
+  CRD_CHECK_ARG(pred && target && acc && dpred && n > 0, "crd_masked_l1_bwd: bad argument");
+  hipLaunchKernelGGL(k_masked_bwd<SMOOTH_L1>, dim3(blocks_for(n, TPB, 2048)), dim3(TPB), 0, as_stream(stream), pred, target,
+                     (long long)n, acc, gout, gmul, 0, dpred);
+  CRD_LAUNCH_CHECK("crd_masked_l1_bwd");
+  return CRD_OK;
+}
 
 extern "C" int crd_masked_dist_fwd(const float* pred, const float* target, int64_t n, crd_sum_t* acc, crd_stream_t stream) {
   CRD_CHECK_ARG(pred && target && acc && n > 0, "crd_masked_dist_fwd: bad argument");
-  hipLaunchKernelGGL(k_masked_dist_fwd, dim3(blocks_for(n, 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc);
+  hipLaunchKernelGGL(k_masked_fwd<DIST>, dim3(blocks_for(n, TPB, 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc,
+                     (unsigned int*)nullptr);
   CRD_LAUNCH_CHECK("crd_masked_dist_fwd");
   return CRD_OK;
 }
@@ -197,8 +259,8 @@ extern "C" int crd_masked_dist_fwd(const float* pred, const float* target, int64
 extern "C" int crd_masked_dist_bwd(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const float* gout,
                                    float gmul, int32_t mode, float* dpred, crd_stream_t stream) {
   CRD_CHECK_ARG(pred && target && acc && dpred && n > 0 && (mode == 0 || mode == 1), "crd_masked_dist_bwd: bad argument");
-  hipLaunchKernelGGL(k_masked_dist_bwd, dim3(blocks_for(n)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc, gout,
-                     gmul, (int)mode, dpred);
+  hipLaunchKernelGGL(k_masked_bwd<DIST>, dim3(blocks_for(n, TPB, 2048)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n,
+                     acc, gout, gmul, (int)mode, dpred);
   CRD_LAUNCH_CHECK("crd_masked_dist_bwd");
   return CRD_OK;
 }
@@ -206,7 +268,7 @@ extern "C" int crd_masked_dist_bwd(const float* pred, const float* target, int64
 extern "C" int crd_masked_berhu_max(const float* pred, const float* target, int64_t n, crd_sum_t* acc, int32_t* maxbits,
                                     crd_stream_t stream) {
   CRD_CHECK_ARG(pred && target && acc && maxbits && n > 0, "crd_masked_berhu_max: bad argument");
-  hipLaunchKernelGGL(k_berhu_max, dim3(blocks_for(n, 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc,
+  hipLaunchKernelGGL(k_masked_fwd<BERHU>, dim3(blocks_for(n, TPB, 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc,
                      reinterpret_cast<unsigned int*>(maxbits));
   CRD_LAUNCH_CHECK("crd_masked_berhu_max");
   return CRD_OK;
@@ -218,7 +280,7 @@ extern "C" int crd_masked_berhu(const float* pred, const float* target, int64_t 
   memcpy(&thresh, &thresh_f64_bits, sizeof thresh);
   CRD_CHECK_ARG(pred && target && acc && maxbits && n > 0 && (loss || dpred) && thresh > 0.0 && isfinite(thresh),
                 "crd_masked_berhu: bad argument");
-  hipLaunchKernelGGL(k_berhu, dim3(blocks_for(n, dpred ? 2048 : 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n,
+  hipLaunchKernelGGL(k_berhu, dim3(blocks_for(n, TPB, dpred ? 2048 : 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n,
                      acc, reinterpret_cast<const unsigned int*>(maxbits), thresh, loss, gout, gmul, dpred);
   CRD_LAUNCH_CHECK("crd_masked_berhu");
   return CRD_OK;
@@ -229,7 +291,7 @@ extern "C" int crd_smoothness_fwd(const float* pred, const float* image, int32_t
   CRD_CHECK_ARG(pred && image && acc && B > 0 && C > 0 && H > 1 && W > 1 && (int64_t)H * W < (1ll << 31) && B <= 65535,
                 "crd_smoothness_fwd: bad argument");
   const int HW = H * W;
-  const int nb = blocks_for(HW, 256);
+  const int nb = blocks_for(HW, TPB, 256);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(k_smooth_sum, dim3(nb, B), dim3(TPB), 0, st, pred, HW, acc);
   hipLaunchKernelGGL(k_smooth_fwd, dim3(nb, B), dim3(TPB), 0, st, pred, image, (int)C, (int)H, (int)W, acc);
@@ -242,8 +304,28 @@ extern "C" int crd_smoothness_bwd(const float* pred, const float* image, int32_t
   CRD_CHECK_ARG(pred && image && acc && dpred && B > 0 && C > 0 && H > 1 && W > 1 && (int64_t)H * W < (1ll << 31) && B <= 65535,
                 "crd_smoothness_bwd: bad argument");
   const int HW = H * W;
-  hipLaunchKernelGGL(k_smooth_bwd, dim3(blocks_for(HW, 256), B), dim3(TPB), 0, as_stream(stream), pred, image, (int)B, (int)C, (int)H,
+  hipLaunchKernelGGL(k_smooth_bwd, dim3(blocks_for(HW, TPB, 256), B), dim3(TPB), 0, as_stream(stream), pred, image, (int)B, (int)C, (int)H,
                      (int)W, acc, gout, gmul, dpred);
   CRD_LAUNCH_CHECK("crd_smoothness_bwd");
+  return CRD_OK;
+}
+
+extern "C" int crd_ce_fwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, crd_sum_t* acc,
+                          crd_stream_t stream) {
+  CRD_CHECK_ARG(logits && labels && acc && B > 0 && C > 0 && HW > 0, "crd_ce_fwd: bad argument");
+  const long long rows = (long long)B * HW;
+  hipLaunchKernelGGL(k_ce_fwd, dim3(blocks_for(rows, TPB, 1024)), dim3(TPB), 0, as_stream(stream), logits,
+                     reinterpret_cast<const long long*>(labels), C, (long long)HW, rows, acc);
+  CRD_LAUNCH_CHECK("crd_ce_fwd");
+  return CRD_OK;
+}
+
+extern "C" int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, const crd_sum_t* acc,
+                                const float* gout, float gmul, float* dlogits, crd_stream_t stream) {
+  CRD_CHECK_ARG(logits && labels && acc && dlogits && B > 0 && C > 0 && HW > 0, "crd_ce_focal_bwd: bad argument");
+  const long long rows = (long long)B * HW;
+  hipLaunchKernelGGL(k_ce_focal_bwd, dim3(blocks_for(rows, TPB, 2048)), dim3(TPB), 0, as_stream(stream), logits,
+                     reinterpret_cast<const long long*>(labels), C, (long long)HW, rows, acc, gout, gmul, dlogits);
+  CRD_LAUNCH_CHECK("crd_ce_focal_bwd");
   return CRD_OK;
 }

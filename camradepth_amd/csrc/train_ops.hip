@@ -1,165 +1,12 @@
-// Training-step kernels for gfx950: masked losses, the multi-tensor diffGradNorm optimizer and the
-// table-driven weight pack / gradient unpack between the reference's parameter layout and the
-// bf16 [Cout][tap][Cin] layout the MFMA kernels read.  All are HBM-bound streaming kernels.
+// Training-step kernels for gfx950: the multi-tensor diffGradNorm optimizer, the table-driven weight pack / gradient unpack between
+// the reference's parameter layout and the bf16 [Cout][tap][Cin] layout the MFMA kernels read, crd_swap_f32 and the dropout
+// masks.  All are HBM-bound streaming kernels.  (The losses are in losses.hip, the evaluation metrics in eval_ops.hip.)
 #include <math.h>
 #include "common.h"
 
 namespace {
 
 constexpr int TPB = 256;
-
-// workgroup sums -> the fixed-point accumulators (order-independent: the loss value and its gradient scale reproduce)
-__device__ __forceinline__ void block_atomic3(float a, float b, float c, crd_sum_t* acc) {
-  a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
-  __shared__ float sm[3][4];
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (l == 0) { sm[0][w] = a; sm[1][w] = b; sm[2][w] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    stat_add(acc + 0, sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3]);
-    stat_add(acc + 1, sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3]);
-    stat_add(acc + 2, sm[2][0] + sm[2][1] + sm[2][2] + sm[2][3]);
-  }
-}
-
-// MaskedSmoothL1Loss / MaskedMSELoss partial sums (loss_funcs.py:40-46, 83-91)
-__global__ __launch_bounds__(TPB) void k_masked_l1_fwd(const float* pred, const float* target, long long n, crd_sum_t* acc) {
-  float s = 0.f, cnt = 0.f, sq = 0.f;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
-    const float t = target[i];
-    if (t > 0.f) {
-      const float e = pred[i] - t, ae = fabsf(e);
-      s += ae < 1.f ? 0.5f * e * e : ae - 0.5f;
-      sq += e * e;
-      cnt += 1.f;
-    }
-  }
-  block_atomic3(s, cnt, sq, acc);
-}
-
-// Trainer.test metrics (runner.py:443-465), per frame f: pred clipped to [0,1] and both scaled by max_depth, ground truth
-// beyond max_distance dropped; acc[f] = (sum |e|, sum e^2, sum |e|/gt, count)
-__global__ __launch_bounds__(TPB) void k_test_metrics(const float* pred, const float* gt, long long n, float max_depth,
-                                                      float max_distance, crd_sum_t* acc) {
-  const int f = blockIdx.y;
-  const float* p = pred + (long long)f * n;
-  const float* g = gt + (long long)f * n;
-  float sa = 0.f, sq = 0.f, sr = 0.f, cnt = 0.f;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
-    float t = g[i] * max_depth;
-    if (t > max_distance) t = 0.f;
-    if (t > 0.f) {
-      const float e = fminf(fmaxf(p[i], 0.f), 1.f) * max_depth - t;
-      sa += fabsf(e); sq += e * e; sr += fabsf(e) / t; cnt += 1.f;
-    }
-  }
-  sa = wave_sum(sa); sq = wave_sum(sq); sr = wave_sum(sr); cnt = wave_sum(cnt);
-  __shared__ float sm[TPB / 64][4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wave][0] = sa; sm[wave][1] = sq; sm[wave][2] = sr; sm[wave][3] = cnt; }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    float v = 0.f;
-    for (int w = 0; w < TPB / 64; ++w) v += sm[w][threadIdx.x];
-    stat_add(&acc[f * 4 + threadIdx.x], v);
-  }
-}
-
-// Confusion matrix of one frame for the Jaccard index of Trainer.test (runner.py:432-436): prediction = arg-max over the C
-// logits of a pixel (NCHW fp32, first maximal class), confmat[f][target][pred] += 1; labels outside [0, C) are counted in
-// oor[f] and skipped (torchmetrics 0.10.2 raises on them, which the reference catches: that frame's IoU stays NaN).
-__global__ __launch_bounds__(TPB) void k_seg_confusion(const float* logits, const long long* labels, int C, long long HW,
-                                                       unsigned long long* confmat, unsigned long long* oor) {
-  extern __shared__ unsigned int hist[];      // C * C + 1
-  const int f = blockIdx.y;
-  for (int i = threadIdx.x; i <= C * C; i += TPB) hist[i] = 0;
-  __syncthreads();
-  const float* lg = logits + (long long)f * C * HW;
-  const long long* lb = labels + (long long)f * HW;
-  for (long long p = (long long)blockIdx.x * TPB + threadIdx.x; p < HW; p += (long long)gridDim.x * TPB) {
-    const long long t = lb[p];
-    if (t < 0 || t >= C) { atomicAdd(&hist[C * C], 1u); continue; }
-    float best = lg[p];
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-      const float v = lg[(long long)c * HW + p];
-      if (v > best) { best = v; arg = c; }
-    }
-    atomicAdd(&hist[(int)t * C + arg], 1u);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < C * C; i += TPB)
-    if (hist[i]) atomicAdd(&confmat[(long long)f * C * C + i], (unsigned long long)hist[i]);
-  if (threadIdx.x == 0 && hist[C * C]) atomicAdd(&oor[f], (unsigned long long)hist[C * C]);
-}
-
-__global__ __launch_bounds__(TPB) void k_masked_l1_bwd(const float* pred, const float* target, long long n, const crd_sum_t* acc,
-                                                       const float* gout, float gmul, float* dpred) {
-  const float g = gmul * (gout ? gout[0] : 1.f) / stat_get(acc + 1);
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
-    const float t = target[i];
-    float d = 0.f;
-    if (t > 0.f) {
-      const float e = pred[i] - t;
-      d = g * fminf(fmaxf(e, -1.f), 1.f);
-    }
-    dpred[i] = d;
-  }
-}
-
-// Cross entropy over NCHW fp32 logits, labels int64 [B][HW], ignore_index 255 (loss_funcs.py:22,27).  Any other label outside
-// [0, C) -- torch raises on it -- never forms an address: the pixel adds nothing to the sum or the count and is counted in acc[2]
-// (as k_seg_confusion counts it in oor[f]); the callers raise on a non-zero count.
-__global__ __launch_bounds__(TPB) void k_ce_fwd(const float* logits, const long long* labels, int C, long long HW, long long rows,
-                                                crd_sum_t* acc) {
-  float s = 0.f, cnt = 0.f, bad = 0.f;
-  for (long long r = (long long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long long)gridDim.x * TPB) {
-    const long long lab = labels[r];
-    if (lab == 255) continue;
-    if (lab < 0 || lab >= C) { bad += 1.f; continue; }
-    const long long b = r / HW, p = r - b * HW;
-    const float* base = logits + (b * C) * HW + p;
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, base[(long long)c * HW]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(base[(long long)c * HW] - mx);
-    // log-sum-exp minus the SHIFTED target logit: (mx + log se) - x[lab] would round at the magnitude of the logits themselves
-    // (5e-4 per pixel for logits near 1e4), x[lab] - mx is small and nearly exact
-    s += logf(se) - (base[lab * HW] - mx);
-    cnt += 1.f;
-  }
-  block_atomic3(s, cnt, bad, acc);
-}
-
-// focal on the scalar mean CE: F=(1-e^-ce)^2 ce ; dF/dce = 2(1-pt)pt ce + (1-pt)^2
-__global__ __launch_bounds__(TPB) void k_ce_focal_bwd(const float* logits, const long long* labels, int C, long long HW,
-                                                      long long rows, const crd_sum_t* acc, const float* gout, float gmul,
-                                                      float* dlogits) {
-  const float cnt = stat_get(acc + 1);
-  const float ce = stat_get(acc) / cnt;
-  const float pt = expf(-ce);
-  const float dF = 2.f * (1.f - pt) * pt * ce + (1.f - pt) * (1.f - pt);
-  const float g = gmul * (gout ? gout[0] : 1.f) * dF / cnt;
-  for (long long r = (long long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long long)gridDim.x * TPB) {
-    const long long lab = labels[r];
-    const long long b = r / HW, p = r - b * HW;
-    const float* base = logits + (b * C) * HW + p;
-    float* dbase = dlogits + (b * C) * HW + p;
-    if (lab == 255 || lab < 0 || lab >= C) {      // ignored, or out of range (counted by k_ce_fwd): no gradient
-      for (int c = 0; c < C; ++c) dbase[(long long)c * HW] = 0.f;
-      continue;
-    }
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, base[(long long)c * HW]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(base[(long long)c * HW] - mx);
-    const float inv = 1.f / se;
-    for (int c = 0; c < C; ++c) {
-      float sm = expf(base[(long long)c * HW] - mx) * inv;
-      dbase[(long long)c * HW] = g * (sm - (c == lab ? 1.f : 0.f));
-    }
-  }
-}
 
 // ---- diffGradNorm (src/models/diffGradNorm.py:73-110) -------------------------------------------
 constexpr int OPT_CHUNK = 4096;  // elements per workgroup
@@ -549,69 +396,7 @@ __global__ __launch_bounds__(TPB) void k_dropout_masks(float* out, const float* 
 }
 __global__ void k_counter_inc(unsigned long long* counter) { *counter += 1; }
 
-inline int blocks_for(long long total, int cap = 2048) {
-  long long n = (total + TPB - 1) / TPB;
-  if (n > cap) n = cap;
-  if (n < 1) n = 1;
-  return (int)n;
-}
-
 }  // namespace
-
-extern "C" int crd_masked_l1_fwd(const float* pred, const float* target, int64_t n, crd_sum_t* acc, crd_stream_t stream) {
-  CRD_CHECK_ARG(pred && target && acc && n > 0, "crd_masked_l1_fwd: bad argument");
-  hipLaunchKernelGGL(k_masked_l1_fwd, dim3(blocks_for(n, 512)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc);
-  CRD_LAUNCH_CHECK("crd_masked_l1_fwd");
-  return CRD_OK;
-}
-
-extern "C" int crd_test_metrics(const float* pred, const float* gt, int32_t frames, int64_t n, float max_depth, float max_distance,
-                                crd_sum_t* acc, crd_stream_t stream) {
-  CRD_CHECK_ARG(pred && gt && acc && frames > 0 && n > 0, "crd_test_metrics: bad argument");
-  hipLaunchKernelGGL(k_test_metrics, dim3(blocks_for(n, 64), frames), dim3(TPB), 0, as_stream(stream), pred, gt, (long long)n,
-                     max_depth, max_distance, acc);
-  CRD_LAUNCH_CHECK("crd_test_metrics");
-  return CRD_OK;
-}
-
-extern "C" int crd_seg_confusion(const float* logits, const int64_t* labels, int32_t frames, int32_t C, int64_t HW, int64_t* confmat,
-                                 int64_t* out_of_range, crd_stream_t stream) {
-  CRD_CHECK_ARG(logits && labels && confmat && out_of_range && frames > 0 && C > 0 && C <= 64 && HW > 0, "crd_seg_confusion: bad argument");
-  hipLaunchKernelGGL(k_seg_confusion, dim3(blocks_for(HW, 128), frames), dim3(TPB), (C * C + 1) * sizeof(unsigned int), as_stream(stream),
-                     logits, reinterpret_cast<const long long*>(labels), C, (long long)HW,
-                     reinterpret_cast<unsigned long long*>(confmat), reinterpret_cast<unsigned long long*>(out_of_range));
-  CRD_LAUNCH_CHECK("crd_seg_confusion");
-  return CRD_OK;
-}
-
-extern "C" int crd_masked_l1_bwd(const float* pred, const float* target, int64_t n, const crd_sum_t* acc, const float* gout,
-                                 float gmul, float* dpred, crd_stream_t stream) {
-  CRD_CHECK_ARG(pred && target && acc && dpred && n > 0, "crd_masked_l1_bwd: bad argument");
-  hipLaunchKernelGGL(k_masked_l1_bwd, dim3(blocks_for(n)), dim3(TPB), 0, as_stream(stream), pred, target, (long long)n, acc, gout,
-                     gmul, dpred);
-  CRD_LAUNCH_CHECK("crd_masked_l1_bwd");
-  return CRD_OK;
-}
-
-extern "C" int crd_ce_fwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, crd_sum_t* acc,
-                          crd_stream_t stream) {
-  CRD_CHECK_ARG(logits && labels && acc && B > 0 && C > 0 && HW > 0, "crd_ce_fwd: bad argument");
-  const long long rows = (long long)B * HW;
-  hipLaunchKernelGGL(k_ce_fwd, dim3(blocks_for(rows, 1024)), dim3(TPB), 0, as_stream(stream), logits,
-                     reinterpret_cast<const long long*>(labels), C, (long long)HW, rows, acc);
-  CRD_LAUNCH_CHECK("crd_ce_fwd");
-  return CRD_OK;
-}
-
-extern "C" int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, const crd_sum_t* acc,
-                                const float* gout, float gmul, float* dlogits, crd_stream_t stream) {
-  CRD_CHECK_ARG(logits && labels && acc && dlogits && B > 0 && C > 0 && HW > 0, "crd_ce_focal_bwd: bad argument");
-  const long long rows = (long long)B * HW;
-  hipLaunchKernelGGL(k_ce_focal_bwd, dim3(blocks_for(rows)), dim3(TPB), 0, as_stream(stream), logits,
-                     reinterpret_cast<const long long*>(labels), C, (long long)HW, rows, acc, gout, gmul, dlogits);
-  CRD_LAUNCH_CHECK("crd_ce_focal_bwd");
-  return CRD_OK;
-}
 
 // ---- diffGradNorm: crd_dgn_desc (include/camradepth_hip.h).  The switches are gate / clip / ema != NULL; the kernels take them as
 // template flags, and dgn_norm / dgn_commit below are the only places that map the one onto the other. ----
@@ -717,7 +502,7 @@ extern "C" int crd_swap_f32(float* a, float* b, int64_t n, crd_stream_t stream) 
   if ((((uintptr_t)(b + head)) & 15) == 0) nvec = (n - head) / 4;
   else head = 0;                                                                      // a and b misaligned differently: one by one
   const long long work = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
-  hipLaunchKernelGGL(k_swap_f32, dim3(blocks_for(work, 4096)), dim3(TPB), 0, as_stream(stream), a, b, (long long)n, head, nvec);
+  hipLaunchKernelGGL(k_swap_f32, dim3(blocks_for(work, TPB, 4096)), dim3(TPB), 0, as_stream(stream), a, b, (long long)n, head, nvec);
   CRD_LAUNCH_CHECK("crd_swap_f32");
   return CRD_OK;
 }
@@ -725,7 +510,7 @@ extern "C" int crd_swap_f32(float* a, float* b, int64_t n, crd_stream_t stream) 
 extern "C" int crd_dropout_masks(float* out, const float* keep, int32_t rows, int32_t cols, uint64_t seed, uint64_t* counter,
                                  crd_stream_t stream) {
   CRD_CHECK_ARG(out && keep && counter && rows > 0 && cols > 0, "crd_dropout_masks: bad argument");
-  hipLaunchKernelGGL(k_dropout_masks, dim3(blocks_for((long long)rows * cols, 64)), dim3(TPB), 0, as_stream(stream), out, keep, rows,
+  hipLaunchKernelGGL(k_dropout_masks, dim3(blocks_for((long long)rows * cols, TPB, 64)), dim3(TPB), 0, as_stream(stream), out, keep, rows,
                      cols, (unsigned long long)seed, reinterpret_cast<unsigned long long*>(counter));
   hipLaunchKernelGGL(k_counter_inc, dim3(1), dim3(1), 0, as_stream(stream), reinterpret_cast<unsigned long long*>(counter));
   CRD_LAUNCH_CHECK("crd_dropout_masks");
@@ -745,7 +530,7 @@ extern "C" int crd_weight_pack(const crd_pack_entry* table_dev, int32_t n, int64
 extern "C" int crd_wgrad_unpack(const crd_unpack_entry* table_dev, int32_t n, int64_t max_elems, int32_t accumulate,
                                 crd_stream_t stream) {
   CRD_CHECK_ARG(table_dev && n > 0 && max_elems > 0, "crd_wgrad_unpack: bad argument");
-  hipLaunchKernelGGL(k_wgrad_unpack, dim3(blocks_for(max_elems, 2048), n), dim3(TPB), 0, as_stream(stream), table_dev, accumulate);
+  hipLaunchKernelGGL(k_wgrad_unpack, dim3(blocks_for(max_elems, TPB, 2048), n), dim3(TPB), 0, as_stream(stream), table_dev, accumulate);
   CRD_LAUNCH_CHECK("crd_wgrad_unpack");
   return CRD_OK;
 }

@@ -8,6 +8,7 @@ exactly with one process per GPU the (sum, count) partials are all-reduced befor
 so the value is the global loss and the local gradient is already divided by the global count
 (gradients are then SUM-reduced across ranks, see parallel.GradSync).
 """
+import collections
 import math
 
 import torch
@@ -22,79 +23,9 @@ def _allreduce_acc(acc):
         dist.all_reduce(acc)
 
 
-class _MaskedL1(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, target, mode):
-        lb = L.load()
-        pred_c, target_c = pred.contiguous().float(), target.contiguous().float()
-        acc = torch.zeros(4, dtype=L.SUM_DTYPE, device=pred.device)     # crd_sum_t: order-independent, exact under all-reduce
-        L.check(lb.crd_masked_l1_fwd(pred_c.data_ptr(), target_c.data_ptr(), pred_c.numel(), acc.data_ptr(), L.stream()),
-                "crd_masked_l1_fwd")
-        _allreduce_acc(acc)
-        ctx.save_for_backward(pred_c, target_c, acc)
-        ctx.mode = mode
-        a = L.stat_checked(acc)              # NaN when a non-finite partial was dropped (the reference's float sums report it)
-        return ((a[0] if mode == "smooth_l1" else a[2]) / a[1]).float()
-
-    @staticmethod
-    def backward(ctx, gout):
-        pred, target, acc = ctx.saved_tensors
-        if ctx.mode != "smooth_l1":
-            raise NotImplementedError("MaskedMSELoss is a metric in the reference (runner.py:208); no backward")
-        lb = L.load()
-        d = torch.empty_like(pred)
-        g = gout.contiguous().float()
-        L.check(lb.crd_masked_l1_bwd(pred.data_ptr(), target.data_ptr(), pred.numel(), acc.data_ptr(), g.data_ptr(), 1.0,
-                                     d.data_ptr(), L.stream()), "crd_masked_l1_bwd")
-        return d, None, None
-
-
-class MaskedSmoothL1Loss(nn.Module):
-    """SmoothL1(beta=1) mean over target > 0 (reference: src/utils/loss_funcs.py:77-91)."""
-
-    def forward(self, pred, target):
-        assert pred.dim() == target.dim(), "inconsistent dimensions"
-        return _MaskedL1.apply(pred, target, "smooth_l1")
-
-
-class MaskedMSELoss(nn.Module):
-    """mean((target-pred)^2) over target > 0 (reference: src/utils/loss_funcs.py:36-46)."""
-
-    def forward(self, pred, target):
-        assert pred.dim() == target.dim(), "inconsistent dimensions"
-        self.loss = _MaskedL1.apply(pred.detach(), target, "mse")
-        return self.loss
-
-
 def _allreduce_max(t):
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-
-
-class _MaskedDist(torch.autograd.Function):
-    """MaskedL1Loss (mode 0) / MaskedRMSELoss (mode 1): one pass for sum |d|, count and sum d^2 (crd_masked_dist_fwd)."""
-
-    @staticmethod
-    def forward(ctx, pred, target, mode):
-        lb = L.load()
-        pred_c, target_c = pred.contiguous().float(), target.contiguous().float()
-        acc = torch.zeros(4, dtype=L.SUM_DTYPE, device=pred.device)
-        L.check(lb.crd_masked_dist_fwd(pred_c.data_ptr(), target_c.data_ptr(), pred_c.numel(), acc.data_ptr(), L.stream()),
-                "crd_masked_dist_fwd")
-        _allreduce_acc(acc)
-        ctx.save_for_backward(pred_c, target_c, acc)
-        ctx.mode = mode
-        a = L.stat_checked(acc)
-        return (a[0] / a[1] if mode == 0 else torch.sqrt(a[2] / a[1])).float()
-
-    @staticmethod
-    def backward(ctx, gout):
-        pred, target, acc = ctx.saved_tensors
-        d = torch.empty_like(pred)
-        g = gout.contiguous().float()
-        L.check(L.load().crd_masked_dist_bwd(pred.data_ptr(), target.data_ptr(), pred.numel(), acc.data_ptr(), g.data_ptr(), 1.0,
-                                             ctx.mode, d.data_ptr(), L.stream()), "crd_masked_dist_bwd")
-        return d, None, None
 
 
 def berhu_value(s1, s2, count, max_abs, thresh):
@@ -105,37 +36,82 @@ def berhu_value(s1, s2, count, max_abs, thresh):
     return (s1 + s2 / (2.0 * c)) / count
 
 
-class _BerHu(torch.autograd.Function):
-    """Phase (a) max |d|, count, sum d^2; the ranks' partials are reduced (SUM, max: MAX); phase (b) the loss sums with the
-    global c; the backward re-runs phase (b) for the gradient only."""
+def _launch(lb, entry, *args):
+    L.check(getattr(lb, entry)(*args, L.stream()), entry)
+
+
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+# The trainable depth criteria, one record per mode: what the loss modules below and the captured step (trainer.TrainStep) launch, and
+# how the value comes from the sums.  pair = (pred, target, n); every pointer is an address or None.
+#   partials(lb, pair, acc, maxbits)      the forward launch into the 4-slot crd_sum_t block acc = (sum, count, sum d^2, -);
+#                                         two_phase: (-, count, sum d^2, -) and the fp32 bits of max |d| in maxbits
+#   grad(lb, pair, acc, maxbits, thresh, loss, gout, gmul, d)
+#                                         the backward launch: d = gmul * gout[0] (1 if None) * dvalue / dpred; two_phase: with it, or with
+#                                         d = None instead of it, the two loss sums into `loss`
+#   value(a, s, max_abs, thresh)          the criterion from the float64 values a of the block (two_phase: s of the loss sums, max |d|)
+#   two_phase                             BerHu: c = thresh * max |d| over ALL ranks comes first; one entry (phase b) then computes the
+#                                         loss sums and the gradient
+Criterion = collections.namedtuple("Criterion", "partials grad value two_phase", defaults=(False,))
+
+
+def _dist(mode, value):      # crd_masked_dist_*: mode 0 L1, mode 1 RMSE
+    return Criterion(lambda lb, pair, acc, mx: _launch(lb, "crd_masked_dist_fwd", *pair, acc),
+                     lambda lb, pair, acc, mx, thresh, loss, gout, gmul, d: _launch(lb, "crd_masked_dist_bwd", *pair, acc, gout, gmul, mode, d),
+                     value)
+
+
+CRITERIA = {
+    "smooth_l1": Criterion(lambda lb, pair, acc, mx: _launch(lb, "crd_masked_l1_fwd", *pair, acc),
+                           lambda lb, pair, acc, mx, thresh, loss, gout, gmul, d: _launch(lb, "crd_masked_l1_bwd", *pair, acc, gout, gmul, d),
+                           lambda a, s, max_abs, thresh: a[0] / a[1]),
+    "l1": _dist(0, lambda a, s, max_abs, thresh: a[0] / a[1]),
+    "rmse": _dist(1, lambda a, s, max_abs, thresh: torch.sqrt(a[2] / a[1])),
+    "berhu": Criterion(lambda lb, pair, acc, mx: _launch(lb, "crd_masked_berhu_max", *pair, acc, mx),
+                       lambda lb, pair, acc, mx, thresh, loss, gout, gmul, d: _launch(lb, "crd_masked_berhu", *pair, acc, mx, L.f64_bits(thresh),
+                                                                                      loss, gout, gmul, d),
+                       lambda a, s, max_abs, thresh: berhu_value(s[0], s[1], a[1], max_abs, thresh), two_phase=True),
+}
+
+
+class _MaskedDepth(torch.autograd.Function):
+    """One criterion of CRITERIA on a (pred, target) pair.  Two-phase (BerHu): phase (a) max |d|, count, sum d^2; the ranks' partials
+    are reduced (SUM, max: MAX); phase (b) the loss sums with the global c; the backward re-runs phase (b) for the gradient only.
+    metric: value(a) of a detached metric on the criterion's partials, which has no backward (MaskedMSELoss)."""
 
     @staticmethod
-    def forward(ctx, pred, target, thresh):
-        lb = L.load()
+    def forward(ctx, pred, target, mode, thresh=None, metric=None):
+        lb, crit, dev = L.load(), CRITERIA[mode], pred.device
         pred_c, target_c = pred.contiguous().float(), target.contiguous().float()
-        acc = torch.zeros(4, dtype=L.SUM_DTYPE, device=pred.device)
-        mx = torch.zeros(1, dtype=torch.int32, device=pred.device)      # fp32 bit pattern of max |d| (non-negative: orders as an int)
-        L.check(lb.crd_masked_berhu_max(pred_c.data_ptr(), target_c.data_ptr(), pred_c.numel(), acc.data_ptr(), mx.data_ptr(),
-                                        L.stream()), "crd_masked_berhu_max")
+        pair = pred_c.data_ptr(), target_c.data_ptr(), pred_c.numel()
+        acc = torch.zeros(4, dtype=L.SUM_DTYPE, device=dev)     # crd_sum_t: order-independent, exact under all-reduce
+        mx = torch.zeros(1, dtype=torch.int32, device=dev) if crit.two_phase else None      # (non-negative floats order as ints)
+        crit.partials(lb, pair, acc.data_ptr(), _addr(mx))
         _allreduce_acc(acc)
-        _allreduce_max(mx)
-        ls = torch.zeros(2, dtype=L.SUM_DTYPE, device=pred.device)
-        L.check(lb.crd_masked_berhu(pred_c.data_ptr(), target_c.data_ptr(), pred_c.numel(), acc.data_ptr(), mx.data_ptr(),
-                                    L.f64_bits(thresh), ls.data_ptr(), None, 0.0, None, L.stream()), "crd_masked_berhu")
-        _allreduce_acc(ls)
+        s = max_abs = None
+        if crit.two_phase:
+            _allreduce_max(mx)
+            ls = torch.zeros(2, dtype=L.SUM_DTYPE, device=dev)
+            crit.grad(lb, pair, acc.data_ptr(), mx.data_ptr(), thresh, ls.data_ptr(), None, 0.0, None)
+            _allreduce_acc(ls)
+            s, max_abs = L.stat_value(ls), mx.view(torch.float32)[0].double()
         ctx.save_for_backward(pred_c, target_c, acc, mx)
-        ctx.thresh = thresh
-        a, s = L.stat_checked(acc), L.stat_value(ls)
-        return berhu_value(s[0], s[1], a[1], mx.view(torch.float32)[0].double(), thresh).float()
+        ctx.mode, ctx.thresh, ctx.metric = mode, thresh, metric is not None
+        a = L.stat_checked(acc)              # NaN when a non-finite partial was dropped (the reference's float sums report it)
+        return (metric(a) if metric else crit.value(a, s, max_abs, thresh)).float()
 
     @staticmethod
     def backward(ctx, gout):
         pred, target, acc, mx = ctx.saved_tensors
+        if ctx.metric:
+            raise NotImplementedError("MaskedMSELoss is a metric in the reference (runner.py:208); no backward")
         d = torch.empty_like(pred)
         g = gout.contiguous().float()
-        L.check(L.load().crd_masked_berhu(pred.data_ptr(), target.data_ptr(), pred.numel(), acc.data_ptr(), mx.data_ptr(),
-                                          L.f64_bits(ctx.thresh), None, g.data_ptr(), 1.0, d.data_ptr(), L.stream()), "crd_masked_berhu")
-        return d, None, None
+        CRITERIA[ctx.mode].grad(L.load(), (pred.data_ptr(), target.data_ptr(), pred.numel()), acc.data_ptr(), _addr(mx), ctx.thresh, None,
+                                g.data_ptr(), 1.0, d.data_ptr())
+        return d, None, None, None, None
 
 
 class _Smoothness(torch.autograd.Function):
@@ -200,37 +176,59 @@ class _Focal(torch.autograd.Function):
         return d, None
 
 
-class MaskedL1Loss(nn.Module):
-    """mean |target - pred| over target > 0 (reference: src/utils/loss_funcs.py:49-59)."""
+class DepthCriterion(nn.Module):
+    """A depth criterion that trains: `mode` names its record in CRITERIA.  trainer.depth_criterion_mode accepts exactly the
+    subclasses of this class."""
+    mode = None
 
     def forward(self, pred, target):
         assert pred.dim() == target.dim(), "inconsistent dimensions"
-        self.loss = _MaskedDist.apply(pred, target, 0)
+        return _MaskedDepth.apply(pred, target, self.mode)
+
+
+class MaskedSmoothL1Loss(DepthCriterion):
+    """SmoothL1(beta=1) mean over target > 0 (reference: src/utils/loss_funcs.py:77-91)."""
+    mode = "smooth_l1"
+
+
+class MaskedMSELoss(nn.Module):
+    """mean((target-pred)^2) over target > 0 (reference: src/utils/loss_funcs.py:36-46): a detached metric on smooth-L1's partials."""
+
+    def forward(self, pred, target):
+        assert pred.dim() == target.dim(), "inconsistent dimensions"
+        self.loss = _MaskedDepth.apply(pred.detach(), target, "smooth_l1", None, lambda a: a[2] / a[1])
         return self.loss
 
 
-class MaskedHuberLoss(nn.Module):
+class MaskedL1Loss(DepthCriterion):
+    """mean |target - pred| over target > 0 (reference: src/utils/loss_funcs.py:49-59)."""
+    mode = "l1"
+
+    def forward(self, pred, target):
+        self.loss = super().forward(pred, target)
+        return self.loss
+
+
+class MaskedHuberLoss(DepthCriterion):
     """nn.HuberLoss() (delta = 1) mean over target > 0 (reference: src/utils/loss_funcs.py:61-75).  Huber with delta = 1 is
     smooth-L1 with beta = 1 term for term, so this runs the MaskedSmoothL1Loss kernels."""
-
-    def forward(self, pred, target):
-        assert pred.dim() == target.dim(), "inconsistent dimensions"
-        return _MaskedL1.apply(pred, target, "smooth_l1")
+    mode = "smooth_l1"
 
 
-class MaskedRMSELoss(nn.Module):
+class MaskedRMSELoss(DepthCriterion):
     """sqrt(mean (target - pred)^2) over target > 0 (reference: src/utils/loss_funcs.py:118-128)."""
+    mode = "rmse"
 
     def forward(self, pred, target):
-        assert pred.dim() == target.dim(), "inconsistent dimensions"
-        self.loss = _MaskedDist.apply(pred, target, 1)
+        self.loss = super().forward(pred, target)
         return self.loss
 
 
-class MaskedBerHuLoss(nn.Module):
+class MaskedBerHuLoss(DepthCriterion):
     """Reverse Huber over target > 0 with c = thresh * max |target - pred| (reference: src/utils/loss_funcs.py:130-155): |d| below
     c, d^2 / (2c) above it, nothing at |d| == c; c is a constant of the backward.  An empty mask gives a NaN loss and a zero
     gradient (the reference's torch.max raises there)."""
+    mode = "berhu"
 
     def __init__(self, thresh=0.2):
         super().__init__()
@@ -240,7 +238,7 @@ class MaskedBerHuLoss(nn.Module):
         assert pred.dim() == target.dim(), "inconsistent dimensions"
         if not (float(self.thresh) > 0.0 and math.isfinite(float(self.thresh))):
             raise L.CrdError(f"MaskedBerHuLoss: thresh must be a finite number > 0, got {self.thresh!r}")
-        return _BerHu.apply(pred, target, float(self.thresh))
+        return _MaskedDepth.apply(pred, target, self.mode, float(self.thresh))
 
 
 class SmoothnessLoss(nn.Module):

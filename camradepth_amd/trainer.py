@@ -18,9 +18,15 @@ import torch.distributed as dist
 
 from . import lib as L
 from . import trace
+from .losses import CRITERIA
 from .optim import _CHUNK, check_ema_decay, check_max_grad_norm, dgn_desc, ema_weight
 
 LOSS_W = (1.0, 1.0, 1.0, 0.2, 0.2)   # runner.py:213
+
+
+def _at(t, offset):
+    """Address `offset` bytes into t, None for no tensor."""
+    return None if t is None else t.data_ptr() + offset
 
 
 def depth_criterion_mode(criterion):
@@ -36,14 +42,12 @@ def depth_criterion_mode(criterion):
     d, sg = criterion["depth"], criterion["seg"]
     if type(sg) is not HL.MaskedFocalLoss:
         raise L.CrdError(f"TrainStep(criterion=...): the seg criterion must be camradepth_amd.losses.MaskedFocalLoss, got {type(sg).__name__}")
-    modes = {HL.MaskedSmoothL1Loss: "smooth_l1", HL.MaskedHuberLoss: "smooth_l1", HL.MaskedL1Loss: "l1", HL.MaskedRMSELoss: "rmse",
-             HL.MaskedBerHuLoss: "berhu"}
-    mode = modes.get(type(d))
+    mode = {cls: cls.mode for cls in HL.DepthCriterion.__subclasses__()}.get(type(d))
     if mode is None:
         raise L.CrdError(f"TrainStep(criterion=...): unsupported depth criterion {type(d).__name__}; the captured step supports "
                          "MaskedSmoothL1Loss, MaskedHuberLoss, MaskedL1Loss, MaskedRMSELoss and MaskedBerHuLoss from camradepth_amd.losses")
     thresh = None
-    if mode == "berhu":
+    if CRITERIA[mode].two_phase:             # BerHu: c = thresh * max |d|
         try:
             thresh = float(d.thresh)
         except (TypeError, ValueError):
@@ -264,7 +268,7 @@ class TrainStep:
                    "quarter": torch.zeros((B, 1, H // 4, W // 4), device=self.dev),
                    "seg": torch.zeros((B, H, W), dtype=torch.int64, device=self.dev)}
         self.acc = torch.zeros(16, dtype=L.SUM_DTYPE, device=self.dev)     # crd_sum_t: 4 x (sum, count, sum sq, -) for full/half/quarter/ce (ce: sum, count, #labels out of range, -)
-        if self._depth_mode == "berhu":
+        if CRITERIA[self._depth_mode].two_phase:
             self.maxbits = torch.zeros(4, dtype=torch.int32, device=self.dev)     # per level: fp32 bits of max |d| (MAX-reduced)
             self.berhu_acc = torch.zeros(8, dtype=L.SUM_DTYPE, device=self.dev)   # per level: (sum part1, sum part2 numerators)
         seg, b2s, nt = self.state.seg_host, self.state.b2s_host, self.state.nt
@@ -381,39 +385,27 @@ class TrainStep:
     # ------------------------------------------------------------------ pieces of one step
     # (class defaults of what is optional: the CPU control-flow tests build the object by hand, tests/trainstep_stub.py)
     _depth_mode, _berhu_thresh, skip_nonfinite = "smooth_l1", None, False
+    maxbits = berhu_acc = None     # BerHu's per-level buffers: no other criterion has them
     grad_hook = None               # tests: called with each bucket's key where that bucket's gradients have become final
     tail_probe = None              # bench.py: a list to collect the main stream's (start, end) events of its wait for the late stream
     late_stream_factory = None     # tools: what makes the late stream instead of torch.cuda.Stream
 
     def _depth_fwd(self, pred, tgt, i):
         """Level i's loss partials into acc[4i:4i+3] = (sum, count, sum d^2) -- BerHu: (-, count, sum d^2) and maxbits[i]."""
-        a, mode = self.acc.data_ptr() + 32 * i, self._depth_mode
-        if mode == "smooth_l1":
-            L.check(self.lib.crd_masked_l1_fwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, L.stream()), "crd_masked_l1_fwd")
-        elif mode == "berhu":
-            L.check(self.lib.crd_masked_berhu_max(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, self.maxbits.data_ptr() + 4 * i,
-                                                  L.stream()), "crd_masked_berhu_max")
-        else:
-            L.check(self.lib.crd_masked_dist_fwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, L.stream()), "crd_masked_dist_fwd")
+        CRITERIA[self._depth_mode].partials(self.lib, (pred.data_ptr(), tgt.data_ptr(), pred.numel()), self.acc.data_ptr() + 32 * i,
+                                            _at(self.maxbits, 4 * i))
 
     def _depth_bwd(self, pred, tgt, d, i, gmul):
-        a, mode = self.acc.data_ptr() + 32 * i, self._depth_mode
-        if mode == "smooth_l1":
-            L.check(self.lib.crd_masked_l1_bwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, None, gmul, d.data_ptr(), L.stream()),
-                    "crd_masked_l1_bwd")
-        elif mode == "berhu":                  # (the loss sums of phase b come with the gradient: losses() reads them)
-            L.check(self.lib.crd_masked_berhu(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, self.maxbits.data_ptr() + 4 * i,
-                                              L.f64_bits(self._berhu_thresh), self.berhu_acc.data_ptr() + 16 * i, None, gmul, d.data_ptr(),
-                                              L.stream()), "crd_masked_berhu")
-        else:
-            L.check(self.lib.crd_masked_dist_bwd(pred.data_ptr(), tgt.data_ptr(), pred.numel(), a, None, gmul,
-                                                 0 if mode == "l1" else 1, d.data_ptr(), L.stream()), "crd_masked_dist_bwd")
+        """Level i's gradient (BerHu: the loss sums of phase b come with it into berhu_acc[2i:2i+2]: losses() reads them)."""
+        CRITERIA[self._depth_mode].grad(self.lib, (pred.data_ptr(), tgt.data_ptr(), pred.numel()), self.acc.data_ptr() + 32 * i,
+                                        _at(self.maxbits, 4 * i), self._berhu_thresh, _at(self.berhu_acc, 16 * i), None, gmul,
+                                        d.data_ptr())
 
     def _reduce_loss_partials(self):
         """The loss point of a multi-GPU step (between the forward and the backward): the global sums and counts -- and BerHu's
         global max |d| per level, which its c and therefore every gradient depend on."""
         dist.all_reduce(self.acc, group=self.sync.group)
-        if self._depth_mode == "berhu":
+        if self.maxbits is not None:
             dist.all_reduce(self.maxbits, op=dist.ReduceOp.MAX, group=self.sync.group)
 
     def _forward_and_loss_partials(self):
@@ -423,7 +415,7 @@ class TrainStep:
             if self.skip_nonfinite:
                 self.gate[:2].zero_()          # a new window: no verdict yet
         self.acc.zero_()
-        if self._depth_mode == "berhu":
+        if self.maxbits is not None:
             self.maxbits.zero_()
             self.berhu_acc.zero_()
         p.forward(pack=False)                  # step() keeps the packed weights current (ensure_packed / _optimizer)
@@ -719,7 +711,7 @@ class TrainStep:
         if self.use_graph and (zero, opt) not in self.graphs:      # e.g. a flush right after an update (last_of_epoch)
             self._capture_iteration()
         self._run(self.graphs[(zero, opt)][0][0] if self.use_graph else self._iteration(late=False))
-        if self.dist_active and self._depth_mode == "berhu":
+        if self.dist_active and self.berhu_acc is not None:
             dist.all_reduce(self.berhu_acc, group=self.sync.group)     # BerHu's loss sums (phase b runs in the backward): losses() only
         if opt:                                # every bucket was re-packed behind its optimizer slice
             self.model.mark_params_changed()
@@ -734,15 +726,10 @@ class TrainStep:
 
     def _level_losses(self, a):
         """full / half / quarter values of the criterion from the host copy `a` of acc (BerHu: one more copy of its sums and maxima)."""
-        n = [a[4 * i + 1] for i in range(3)]
-        if self._depth_mode == "rmse":
-            return [float(torch.sqrt(a[4 * i + 2] / n[i])) for i in range(3)]
-        if self._depth_mode == "berhu":
-            from .losses import berhu_value
-            b = L.stat_value(self.berhu_acc.cpu())
-            mx = self.maxbits.cpu().view(torch.float32).double()
-            return [float(berhu_value(b[2 * i], b[2 * i + 1], n[i], mx[i], self._berhu_thresh)) for i in range(3)]
-        return [float(a[4 * i] / n[i]) for i in range(3)]         # smooth-L1 (Huber) / L1: sum / count
+        b = L.stat_value(self.berhu_acc.cpu()).view(4, 2) if self.berhu_acc is not None else [None] * 3
+        mx = self.maxbits.cpu().view(torch.float32).double() if self.maxbits is not None else [None] * 3
+        value = CRITERIA[self._depth_mode].value
+        return [float(value(a[4 * i:4 * i + 4], b[i], mx[i], self._berhu_thresh)) for i in range(3)]
 
     def losses(self):
         """Host view of the last iteration's loss terms (synchronises): the criterion's value per depth level; "rmse" is

@@ -945,9 +945,9 @@ int crd_ce_fwd(const float* logits, const int64_t* labels, int32_t B, int32_t C,
 int crd_ce_focal_bwd(const float* logits, const int64_t* labels, int32_t B, int32_t C, int64_t HW, const crd_sum_t* acc,
                      const float* gout, float gmul, float* dlogits, crd_stream_t stream);
 
-/* More depth criteria (loss_funcs.py:49-59,118-180; camradepth_amd/csrc/losses.hip).  MaskedHuberLoss (nn.HuberLoss, delta = 1) is
- * smooth-L1 with beta = 1 and runs crd_masked_l1_fwd / _bwd.  d = pred - target over target > 0; crd_sum_t sums with
- * CRD_STAT_FRAC_BITS, zeroed by the caller. */
+/* More depth criteria (loss_funcs.py:49-59,118-180; camradepth_amd/csrc/losses.hip, as every loss above).  MaskedHuberLoss
+ * (nn.HuberLoss, delta = 1) is smooth-L1 with beta = 1 and runs crd_masked_l1_fwd / _bwd.  d = pred - target over target > 0;
+ * crd_sum_t sums with CRD_STAT_FRAC_BITS, zeroed by the caller. */
 /* MaskedL1Loss / MaskedRMSELoss: acc[0] += sum |d|, acc[1] += #(target>0), acc[2] += sum d^2
  * (L1 = acc0/acc1, RMSE = sqrt(acc2/acc1)) */
 int crd_masked_dist_fwd(const float* pred, const float* target, int64_t n, crd_sum_t* acc, crd_stream_t stream);
