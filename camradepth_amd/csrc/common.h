@@ -50,6 +50,12 @@ static inline void crd_reserve_lds(const void* fn, int bytes, const char* kernel
   const hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e_ != hipSuccess) crd_note_attr_failure(kernel, bytes, (int)e_);
 }
+// ... made once per process and kernel: KERNEL is a template argument, so every template instance of a kernel has its own flag
+template <auto KERNEL>
+static inline void crd_reserve_lds_once(int bytes, const char* kernel) {
+  static bool done = false;
+  if (!done) { crd_reserve_lds(reinterpret_cast<const void*>(KERNEL), bytes, kernel); done = true; }
+}
 
 #define CRD_LAUNCH_CHECK(name)                                                   \
   do {                                                                           \
@@ -99,6 +105,9 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0); vmcnt / expcnt untouched
   asm volatile("s_barrier" ::: "memory");
 }
+// counted wait of the kernels that keep LDS-DMA requests in flight: at most N of this wave's vector-memory requests still outstanding
+template <int N>
+__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // two fp32 -> packed bf16 pair with the hardware converter (v_cvt_pk_bf16_f32, round-to-nearest-even)
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;

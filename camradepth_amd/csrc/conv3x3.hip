@@ -65,9 +65,6 @@ __device__ unsigned long long g_prof[4][8];
 #define ABL(bit) false
 #endif
 
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 constexpr int QK = 32;                      // channels per chunk: 64-byte LDS rows, 4 granules
 constexpr int QNW = 4;                      // waves per workgroup
 constexpr int QHG = (HROWS + 15) / 16;      // 22 halo DMA pieces (16 rows x 64 B each)
@@ -293,18 +290,11 @@ int launch3(const ConvK& k0, int B, hipStream_t st, long long partial_cap, int c
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   const int tiles_x = cdiv(k.IW, TW), tiles_y = cdiv(k.IH, TH);
   dim3 grid(tiles_x * tiles_y, cdiv(col1 - col0, BN), B);
-  static bool attr_done[2] = {false, false};
   if (k.gather_mode == 0) {
-    if (!attr_done[0]) {
-      crd_reserve_lds(reinterpret_cast<const void*>(&k_conv3x3<WM, WN, TM, TN, 0, WS>), (int)lds, "k_conv3x3");
-      attr_done[0] = true;
-    }
+    crd_reserve_lds_once<&k_conv3x3<WM, WN, TM, TN, 0, WS>>((int)lds, "k_conv3x3");
     hipLaunchKernelGGL((k_conv3x3<WM, WN, TM, TN, 0, WS>), grid, dim3(256), lds, st, k, tiles_x);
   } else {
-    if (!attr_done[1]) {
-      crd_reserve_lds(reinterpret_cast<const void*>(&k_conv3x3<WM, WN, TM, TN, 1, WS>), (int)lds, "k_conv3x3");
-      attr_done[1] = true;
-    }
+    crd_reserve_lds_once<&k_conv3x3<WM, WN, TM, TN, 1, WS>>((int)lds, "k_conv3x3");
     hipLaunchKernelGGL((k_conv3x3<WM, WN, TM, TN, 1, WS>), grid, dim3(256), lds, st, k, tiles_x);
   }
   if (finalize && k.stats && k.stats_partial)

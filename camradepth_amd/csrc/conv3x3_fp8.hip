@@ -35,8 +35,7 @@ typedef __attribute__((ext_vector_type(8))) int i32x8;
 #endif
 
 template <int N>
-__device__ __forceinline__ void wait_vm() {
-  if (ABL(16)) return; asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void wait_vm_abl() { if (!ABL(16)) wait_vm<N>(); }      // common.h's counted wait, unless ablated
 
 struct F8K {
   const unsigned char* x; int x_ld; long long x_bstride;     // fp8 activations [B][H*W][x_ld]
@@ -172,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fp8(F8K a, int tiles_x, int 
     stage_weights(pc, pt, s);
     if (++pt == 9) { pt = 0; if (++pc == nChunks) pc = 0; }
   }
-  wait_vm<(D - 2) * WJ>();                            // halo + slabs 0 and 1 (step 0 reads the fragments of step 1)
+  wait_vm_abl<(D - 2) * WJ>();                            // halo + slabs 0 and 1 (step 0 reads the fragments of step 1)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // (also publishes sS)
   int gchunk = 0, wb = 0, wnext = D % WS;
   i32x8 fa[TM], fb[TN], nb[TN];
@@ -236,8 +235,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fp8(F8K a, int tiles_x, int 
         // plus this chunk's halo burst (issued before tap 0's slab request) while tap <= D-3.
         // (no lgkmcnt wait here: LDS reads return in order and the next step waits for these fragments before its barrier,
         // so every read is done at least one barrier before its slot or halo buffer is written again)
-        if (tap <= D - 3) wait_vm<(D - 2) * WJ + HT>();
-        else wait_vm<(D - 2) * WJ>();
+        if (tap <= D - 3) wait_vm_abl<(D - 2) * WJ + HT>();
+        else wait_vm_abl<(D - 2) * WJ>();
         if (!ABL(32)) __builtin_amdgcn_s_barrier();
         wb = wb1;
         wnext = wnext + 1 == WS ? 0 : wnext + 1;
@@ -351,7 +350,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_fp8(F8K a, int tiles_x, int 
       read_b(wb, fb);
     }
   }
-  wait_vm<0>();
+  wait_vm_abl<0>();
 }
 
 template <int TN, int MODE = 0>
@@ -364,8 +363,7 @@ int launch8(const F8K& k, int B, hipStream_t st) {
   if (gx < 1) gx = 1;
   if (gx > tiles_total) gx = tiles_total;
   const size_t lds = (size_t)(2 * HPAD * QKC + WS * BN * QKC + 16 * QKC) + BN * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) { crd_reserve_lds(reinterpret_cast<const void*>(&k_conv3x3_fp8<TN, WS, MODE>), (int)lds, "k_conv3x3_fp8"); attr_done = true; }
+  crd_reserve_lds_once<&k_conv3x3_fp8<TN, WS, MODE>>((int)lds, "k_conv3x3_fp8");
   hipLaunchKernelGGL((k_conv3x3_fp8<TN, WS, MODE>), dim3(gx, gy), dim3(256), lds, st, k, tiles_x, tiles_y, tiles_total);
   CRD_LAUNCH_CHECK("crd_conv3x3_fp8");
   return CRD_OK;

@@ -42,9 +42,6 @@ constexpr int HPAD = HG * 16;              // 624 rows allocated per halo buffer
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4w;
 #ifndef CRD_C3P_WS
 #define CRD_C3P_WS 5
@@ -390,13 +387,12 @@ int launch_p(const ConvK& k0, int B, hipStream_t st, int col0, int col1) {
   if (gx < 1) gx = 1;
   if (gx > tiles_total) gx = tiles_total;
   const size_t lds = (size_t)(2 * HPAD * QK + WS * BN * QK + 16 * QK) * sizeof(bf16_t);
-  static bool attr_done[2] = {false, false};
   const int m = k.gather_mode == 0 ? 0 : 1;
   if (m == 0) {
-    if (!attr_done[0]) { crd_reserve_lds(reinterpret_cast<const void*>(&k_conv3x3p<TN, 0, WS, NW>), (int)lds, "k_conv3x3p"); attr_done[0] = true; }
+    crd_reserve_lds_once<&k_conv3x3p<TN, 0, WS, NW>>((int)lds, "k_conv3x3p");
     hipLaunchKernelGGL((k_conv3x3p<TN, 0, WS, NW>), dim3(gx, gy), dim3(64 * NW), lds, st, k, tiles_x, tiles_y, tiles_total);
   } else {
-    if (!attr_done[1]) { crd_reserve_lds(reinterpret_cast<const void*>(&k_conv3x3p<TN, 1, WS, NW>), (int)lds, "k_conv3x3p"); attr_done[1] = true; }
+    crd_reserve_lds_once<&k_conv3x3p<TN, 1, WS, NW>>((int)lds, "k_conv3x3p");
     hipLaunchKernelGGL((k_conv3x3p<TN, 1, WS, NW>), dim3(gx, gy), dim3(64 * NW), lds, st, k, tiles_x, tiles_y, tiles_total);
   }
   CRD_LAUNCH_CHECK("crd_conv_igemm(3x3 persistent)");

@@ -4,6 +4,8 @@
 
 namespace crdk {
 
+// One definition of how the block is filled: convk_from_desc() below.  A NEW FIELD IS SET THERE AND NOWHERE ELSE; the entry points and
+// launch functions override only what is theirs (named at convk_from_desc).
 struct ConvK {
   const bf16_t* x; int x_ld; int IH, IW, Cin; long long x_bstride;
   const bf16_t* w; int Cout, KW, stride, pad, Ktot;
@@ -27,6 +29,38 @@ struct ConvK {
   int dbg;   // developer experiments only (CRD_DBG env): 1 no weight-DMA wait, 2 no DMA at all, 4 no epilogue
   int ny_tiles;   // column tiles of the launch, for kernels that decode (row tile, column tile) from a 1-D XCD-aware grid (xfgemm.hip)
 };
+
+// ConvK of a descriptor that has passed its entry point's checks: every field that is a pure function of the descriptor; the rest is
+// zero.  Set elsewhere, and only there: stats_partial (crd_conv_igemm), x = nullptr (crd_gn_conv: the operand travels in GnIn),
+// gather_mode = 0 (crd_gn_bwd_conv), and per launch n_tiles, lds_bytes, col0 (conv3x3.hip) and ny_tiles (xfgemm.hip).
+inline void convk_from_desc(const crd_conv_desc& d, ConvK& k) {
+  static const int dbg = crd_dev_int("CRD_DBG", 0);
+  k = ConvK{};
+  k.x = reinterpret_cast<const bf16_t*>(d.x) + d.x_coff; k.x_ld = d.x_ld;
+  k.IH = d.IH; k.IW = d.IW; k.Cin = d.Cin; k.x_bstride = (long long)d.IH * d.IW * d.x_ld;
+  k.w = reinterpret_cast<const bf16_t*>(d.w);
+  k.Cout = d.Cout; k.KW = d.KW; k.stride = d.stride; k.pad = d.pad; k.Ktot = d.KH * d.KW * d.Cin;
+  k.OW = d.OW; k.OHW = d.OH * d.OW; k.gather_mode = d.gather_mode;
+  k.y_ld = d.y_ld; k.y_f32 = d.y_f32;
+  k.out_mode = d.out_mode; k.patch_k = d.patch_k; k.patch_c = d.patch_c;
+  int YH = d.OH, YW = d.OW;                            // the output image: patch_k times the GEMM's pixel grid under the patch scatter
+  if (d.out_mode == 1) { YH = d.OH * d.patch_k; YW = d.OW * d.patch_k; }
+  k.YW = YW;
+  k.y_bstride = (long long)YH * YW * d.y_ld;
+  k.y = d.y_f32 ? (void*)(reinterpret_cast<float*>(d.y) + d.y_coff) : (void*)(reinterpret_cast<bf16_t*>(d.y) + d.y_coff);
+  k.bias = d.bias; k.bias_bstride = d.bias_bstride; k.act = d.act;
+  k.res = d.res; k.res_ld = d.res_ld; k.res_bstride = (long long)YH * YW * d.res_ld; k.res_scale = d.res_scale;
+  k.accumulate = d.accumulate; k.stats = d.stats; k.G16 = d.Cout / 16;
+  k.chan = d.chan_sums;
+  k.vec_ok = (d.y_coff % 8 == 0) && ((reinterpret_cast<uintptr_t>(d.y) & 15) == 0);
+  k.vecf_ok = d.y_f32 && d.y_coff % 4 == 0 && d.y_ld % 4 == 0 && d.Cout % 4 == 0 && (reinterpret_cast<uintptr_t>(d.y) & 15) == 0 &&
+              (!d.res || (d.res_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(d.res) & 15) == 0));
+  k.red_x = d.red_x; k.red_x_f32 = d.red_x_f32; k.red_x_ld = d.red_x_ld;
+  k.red_x_bstride = (long long)YH * YW * d.red_x_ld;
+  k.red_stats = d.red_stats; k.red_gamma = d.red_gamma; k.red_beta = d.red_beta; k.red_gmul = d.red_gmul;
+  k.red_act = d.red_act; k.red_r = d.red_r;
+  k.dbg = dbg;
+}
 
 
 // fp32 LDS-staged epilogue (conv_epilogue's second branch) applies?  One definition for conv_epilogue and conv_epilogue_idle.
@@ -518,9 +552,12 @@ __device__ __forceinline__ void conv_epilogue_idle(const ConvK& a) {
 // GroupNorm + exact GELU applied to the bf16 input rows on their way in (Mlp.norm2 in front of fc2); xn: optional bf16 copy of the
 // activated rows (what fc2's weight gradient reads).
 struct NarrowGn {
-  const crd_sum_t* stats; int gmul; const float* gamma; const float* beta; float count;
-  bf16_t* xn; int xn_ld; long long xn_bstride;
+  const crd_sum_t* stats; int gmul;       // [B][Cin/16][2] slab sums of x; a group = gmul slabs
+  const float* gamma; const float* beta;  // [Cin]
+  float count;                            // pixels per sample * channels per group
+  bf16_t* xn; int xn_ld; long long xn_bstride;    // optional store of act(GN(x)) (bf16), nullptr = none
 };
+constexpr NarrowGn NARROW_GN_NONE = {nullptr, 1, nullptr, nullptr, 1.f, nullptr, 0, 0};     // no GroupNorm in front: plain rows
 
 // stats[b][g][which] += sum over tiles of the per-tile partials written by conv_epilogue
 __global__ __launch_bounds__(256) void k_stats_finalize(const float* partial, int n_tiles, int G16, crd_sum_t* stats);

@@ -1018,14 +1018,13 @@ extern "C" int crd_dwconv3x3_wgrad(const void* x, const void* dy, int32_t B, int
   const bf16_t* xp = reinterpret_cast<const bf16_t*>(x);
   const bf16_t* dp = reinterpret_cast<const bf16_t*>(dy);
   hipStream_t st = as_stream(stream);
-  static bool attr_done[2] = {false, false};
   if (tw == 32) {
     const size_t lds = (size_t)((DTH + 2) * 34 * 8 + DTH * 32 * 8) * sizeof(uint4);
-    if (!attr_done[0]) { crd_reserve_lds(reinterpret_cast<const void*>(&k_dwconv_wgrad<32>), (int)lds, "k_dwconv_wgrad"); attr_done[0] = true; }
+    crd_reserve_lds_once<&k_dwconv_wgrad<32>>((int)lds, "k_dwconv_wgrad");
     hipLaunchKernelGGL(k_dwconv_wgrad<32>, grid, dim3(TPB), lds, st, xp, dp, H, W, C, dw10, replicas, tiles_x, tiles_y, per, inn);
   } else {
     const size_t lds = (size_t)((DTH + 2) * 18 * 8 + DTH * 16 * 8) * sizeof(uint4);
-    if (!attr_done[1]) { crd_reserve_lds(reinterpret_cast<const void*>(&k_dwconv_wgrad<16>), (int)lds, "k_dwconv_wgrad"); attr_done[1] = true; }
+    crd_reserve_lds_once<&k_dwconv_wgrad<16>>((int)lds, "k_dwconv_wgrad");
     hipLaunchKernelGGL(k_dwconv_wgrad<16>, grid, dim3(TPB), lds, st, xp, dp, H, W, C, dw10, replicas, tiles_x, tiles_y, per, inn);
   }
   CRD_LAUNCH_CHECK("crd_dwconv3x3_wgrad");
@@ -1190,11 +1189,7 @@ static int attn_scores_bwd_launch(const void* q, const void* k, const float* dS,
   int nblk = attn_bwd_blocks(B, N, M, heads, C);
   const int use_lds = nblk > 0;
   CRD_CHECK_ARG(use_lds ? (dk_partials || dk) : dk != nullptr, "%s: this shape needs the dk accumulator", who);
-  static bool attr_done = false;
-  if (!attr_done) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_attn_scores_bwd), 128 * 1024, "k_attn_scores_bwd");
-    attr_done = true;
-  }
+  crd_reserve_lds_once<&k_attn_scores_bwd>(128 * 1024, "k_attn_scores_bwd");
   if (!use_lds) {
     nblk = cdiv(N, 64);
     int cap = 2048 / (B > 0 ? B : 1); if (cap < 1) cap = 1;

@@ -20,81 +20,37 @@
 // pair as well.  This one uses lds_barrier() (common.h) and matches or beats the pair on every shape without GELU.
 // The epilogue (bias, residual + DropPath scale, GroupNorm sums of the output, fp32 / bf16 stores) is conv_common.h's.
 #include <stdlib.h>
-#include "conv_common.h"
+#include "reg_gemm.h"
 
 using namespace crdk;
 
 namespace {
 
-constexpr int BK = 64;
-
+// the operand: raw rows and the GroupNorm applied to them (conv_common.h: NarrowGn, NARROW_GN_NONE for plain rows)
 struct GnIn {
   const void* x; int x_f32;               // raw input [B][IH*IW][x_ld] (+ channel offset applied), fp32 or bf16
-  const crd_sum_t* stats; int gmul;       // [B][Cin/16][2] slab sums of x; a group = gmul slabs
-  const float* gamma; const float* beta;  // [Cin]
-  float count;                            // pixels per sample * channels per group
-  bf16_t* xn; int xn_ld; long long xn_bstride;    // optional store of act(GN(x)) (bf16), nullptr = none
+  NarrowGn gn;
 };
-
 
 // (scale, shift) of every input channel of sample b -> tab[Cin]
 __device__ __forceinline__ void build_table(const ConvK& a, const GnIn& gi, int b, float2* tab) {
-  const crd_sum_t* stb = gi.stats + (long long)b * (a.Cin >> 4) * 2;
+  const crd_sum_t* stb = gi.gn.stats + (long long)b * (a.Cin >> 4) * 2;
   for (int c = threadIdx.x; c < a.Cin; c += 256) {
     float mean, rstd;
-    gn_mean_rstd(stb, ((c >> 4) / gi.gmul) * gi.gmul, gi.gmul, gi.count, mean, rstd);
-    const float ga = gi.gamma[c] * rstd;
-    tab[c] = make_float2(ga, gi.beta[c] - mean * ga);
+    gn_mean_rstd(stb, ((c >> 4) / gi.gn.gmul) * gi.gn.gmul, gi.gn.gmul, gi.gn.count, mean, rstd);
+    const float ga = gi.gn.gamma[c] * rstd;
+    tab[c] = make_float2(ga, gi.gn.beta[c] - mean * ga);
   }
 }
-
-template <int TM, int TN, int WM, int WN>
-__device__ __forceinline__ void mfma_slab(const bf16_t* sa, const bf16_t* sb, f32x16 (&acc)[TM][TN], int wm, int wn, int l) {
-#pragma unroll
-  for (int ks = 0; ks < BK / 16; ++ks) {
-    bf16x8 af[TM], bfr[TN];
-    const int gi2 = ks * 2 + (l >> 5);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = (wm * TM + i) * 32 + (l & 31);
-      af[i] = *reinterpret_cast<const bf16x8*>(&sa[row * BK + ((gi2 ^ ((row >> 1) & 7)) << 3)]);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = (wn * TN + j) * 32 + (l & 31);
-      bfr[j] = *reinterpret_cast<const bf16x8*>(&sb[row * BK + ((gi2 ^ ((row >> 1) & 7)) << 3)]);
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-  }
-}
-
-template <int TM, int TN, int WN>
-__device__ __forceinline__ void init_acc(const ConvK& a, f32x16 (&acc)[TM][TN], int b, int n0, int wn, int l) {
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = n0 + (wn * TN + j) * 32 + (l & 31);
-    const float bias_v = (a.bias && col < a.Cout) ? a.bias[(long long)b * a.bias_bstride + col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = bias_v;
-  }
-}
-
-template <int BM, int BN>
-constexpr size_t epilogue_bytes() { return (size_t)BM * (BN + 8) * 4 + 256 * 16 * 4 + 2048; }   // fp32 staging tile + folds behind it
 
 // One workgroup per (row tile, column tile) like k_igemm; 32-48 KB of LDS, so 3-4 workgroups per CU hide each other's
 // latencies; no counted waits (the compiler tracks register loads exactly, lds_barrier() keeps them in flight across barriers).
+// The skeleton -- per-thread constants, weight half of a slab, K loop -- is reg_gemm.h's.
 template <int WM, int WN, int TM, int TN, int XF32, int ACT>
 __device__ __forceinline__ void gngemm_body(const ConvK& a, const GnIn& gi, const int bx, const int by, const int bz) {
   static_assert(WM * WN == 4, "4 waves");
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int A_IT = BM / 32, B_IT = BN / 32;
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4r;
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
   bf16_t* sA = lds;                                   // [2][BM][BK]   (the epilogue's staging area aliases the tiles)
   bf16_t* sB = sA + 2 * BM * BK;                      // [2][BN][BK]
@@ -104,26 +60,23 @@ __device__ __forceinline__ void gngemm_body(const ConvK& a, const GnIn& gi, cons
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wv / WN, wn = wv % WN;
   const int b = bz, m0 = bx * BM, n0 = by * BN;
-  const int r0 = 8 * wv + (l >> 3);                   // this thread's rows: r0 + 32 i; LDS slot l & 7 <- K granule g (k_igemm's swizzle)
-  const int g = (l & 7) ^ ((r0 >> 1) & 7);
-  const unsigned OOB = 0x80000000u;
+  const RegLane ln = reg_lane(wv, l);
+  const int r0 = ln.r0, g = ln.g;                     // this thread's rows: r0 + 32 i; LDS slot l & 7 <- K granule g
   const int esz = XF32 ? 4 : 2;
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(reinterpret_cast<const char*>(gi.x) + (long long)b * a.x_bstride * esz), 0, (int)(a.x_bstride * esz), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.Cout * a.Ktot * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = reg_weight_rsrc(a);
   const int nK = (a.Ktot + BK - 1) / BK;
-  const bool store_xn = gi.xn != nullptr && by == 0;
+  const bool store_xn = gi.gn.xn != nullptr && by == 0;
   // the stored copy of the normalised operand goes through a buffer descriptor: rows / granules that are not stored carry an
-  // out-of-range offset and the hardware drops them, so the store is UNCONDITIONAL (round 6: under `if (store_xn && ok)` the compiler
-  // could no longer count the requests in flight and drained the two-slab prefetch at every use -- see the K loop below)
+  // out-of-range offset and the hardware drops them, so the store is UNCONDITIONAL (reg_gemm.h: THE K LOOP says why)
   const __amdgpu_buffer_rsrc_t rxn = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(store_xn ? gi.xn + (long long)b * gi.xn_bstride : reinterpret_cast<bf16_t*>(const_cast<bf16_t*>(a.w))), 0,
-      store_xn ? (int)(gi.xn_bstride * 2) : 0, 0x00020000);
+      (void*)(store_xn ? gi.gn.xn + (long long)b * gi.gn.xn_bstride : reinterpret_cast<bf16_t*>(const_cast<bf16_t*>(a.w))), 0,
+      store_xn ? (int)(gi.gn.xn_bstride * 2) : 0, 0x00020000);
 
   // per-row constants: pixel index of the row's patch origin, validity; and the loop-invariant BYTE offsets of that origin in x / xn
   // with the validity folded in (an invalid row starts out of range and stays there whatever the K loop adds): every load and store of
-  // the K loop is unconditional.  As `ok ? computed : OOB` inside the loop the compiler sank the multiply into an exec-mask branch
-  // around the load (two loads into the same registers on two paths, each behind a vmcnt(0)) in the bf16-input variants.
+  // the K loop is unconditional
   int rowpix[A_IT];
   bool rowok[A_IT];
   unsigned rowoff[A_IT], xnoff[A_IT];
@@ -134,14 +87,10 @@ __device__ __forceinline__ void gngemm_body(const ConvK& a, const GnIn& gi, cons
     rowok[i] = m < a.OHW;
     rowpix[i] = oy * a.stride * a.IW + ox * a.stride;
     rowoff[i] = rowok[i] ? (unsigned)(rowpix[i] * a.x_ld * esz) : OOB;
-    xnoff[i] = (rowok[i] && store_xn) ? (unsigned)(rowpix[i] * gi.xn_ld * 2) : OOB;
+    xnoff[i] = (rowok[i] && store_xn) ? (unsigned)(rowpix[i] * gi.gn.xn_ld * 2) : OOB;
   }
   unsigned woff[B_IT];
-#pragma unroll
-  for (int j = 0; j < B_IT; ++j) {
-    const int ng = n0 + r0 + 32 * j;
-    woff[j] = ng < a.Cout ? (unsigned)(ng * a.Ktot * 2) : OOB;
-  }
+  reg_weight_offsets(a, n0, r0, woff);
   struct Regs { u32x4r a[A_IT][XF32 ? 2 : 1]; u32x4r w[B_IT]; };
   auto kpos = [&](int kt, int& kc, int& tappix, bool& kok) {     // this thread's K granule of slab kt: channel, pixel offset of its tap
     const int kf = kt * BK + g * 8;
@@ -160,9 +109,7 @@ __device__ __forceinline__ void gngemm_body(const ConvK& a, const GnIn& gi, cons
       r.a[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
       if (XF32) r.a[i][XF32 ? 1 : 0] = __builtin_amdgcn_raw_buffer_load_b128(rx, off + 16, 0, 0);
     }
-#pragma unroll
-    for (int j = 0; j < B_IT; ++j)
-      r.w[j] = __builtin_amdgcn_raw_buffer_load_b128(rw, (woff[j] + (unsigned)((kt * BK + g * 8) * 2)) | km, 0, 0);
+    reg_load_weights(rw, woff, kt * BK + g * 8, km, r.w);
   };
   auto store_slab = [&](int kt, int stage, const Regs& r) {
     int kc, tappix; bool kok;
@@ -196,7 +143,7 @@ __device__ __forceinline__ void gngemm_body(const ConvK& a, const GnIn& gi, cons
       }
       const u32x4r q = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
       *reinterpret_cast<u32x4r*>(sA + stage * BM * BK + (r0 + 32 * i) * BK + (l & 7) * 8) = q;
-      __builtin_amdgcn_raw_buffer_store_b128(q, rxn, (xnoff[i] + (unsigned)((tappix * gi.xn_ld + kc) * 2)) | (kok ? 0u : OOB), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(q, rxn, (xnoff[i] + (unsigned)((tappix * gi.gn.xn_ld + kc) * 2)) | (kok ? 0u : OOB), 0, 0);
     }
 #pragma unroll
     for (int j = 0; j < B_IT; ++j) *reinterpret_cast<u32x4r*>(sB + stage * BN * BK + (r0 + 32 * j) * BK + (l & 7) * 8) = r.w[j];
@@ -210,15 +157,11 @@ __device__ __forceinline__ void gngemm_body(const ConvK& a, const GnIn& gi, cons
   load_slab(1, r1s);                                  // (slabs past the end: every offset out of range -- zeros, no traffic)
   f32x16 acc[TM][TN];
   init_acc<TM, TN, WN>(a, acc, b, n0, wn, l);
+  // the K loop: reg_gemm.h (THE K LOOP) has the rules -- no conditional memory operation in it -- and says why it is written out here
   lds_barrier();                                      // the table
   store_slab(0, 0, r0s);
   load_slab(2, r0s);
   lds_barrier();
-  // Steady state, two slabs per trip and NO conditional memory operation in it (round 6).  With `if (kt + 3 < nK) load_slab(...)` --
-  // a wave-uniform branch around six loads -- the number of requests in flight depends on the path, and the compiler's wait insertion
-  // assumes the path that issued fewer: every use of a slab's registers then also drained the YOUNGER slab's requests
-  // (s_waitcnt vmcnt(5..0) in the ISA where vmcnt(12..9) was meant), i.e. the two-slab prefetch was one slab deep.  Slabs past the end
-  // carry out-of-range offsets instead (zeros in, nothing out); an odd slab count ends in a single-slab tail.
   int kt = 0;
   for (; kt + 2 <= nK; kt += 2) {
     store_slab(kt + 1, 1, r1s);
@@ -265,17 +208,11 @@ int launch_reg2(const ConvK& k0, const GnIn& g0, const ConvK& k1, const GnIn& g1
   p.nt0 = p.a0.n_tiles = cdiv(k0.OHW, BM); p.nt1 = p.a1.n_tiles = cdiv(k1.OHW, BM);
   p.nb0 = p.nt0 * cdiv(k0.Cout, BN);
   const int nb1 = p.nt1 * cdiv(k1.Cout, BN);
-  size_t tiles = (size_t)2 * (BM + BN) * BK * 2;
-  if (tiles < epilogue_bytes<BM, BN>()) tiles = epilogue_bytes<BM, BN>();
-  tiles = (tiles + 255) / 256 * 256;
+  constexpr size_t tiles = reg_gemm_tile_bytes<BM, BN>();
   const int cin = k0.Cin > k1.Cin ? k0.Cin : k1.Cin;
   const size_t lds = tiles + (size_t)cin * sizeof(float2);
-  CRD_UNSUPPORTED(lds <= 160 * 1024, "crd_gn_conv2: table does not fit in LDS");
-  static bool attr_done = false;
-  if (!attr_done) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_gngemm_reg2<WM, WN, TM, TN, XF32, ACT>), 160 * 1024, "k_gngemm_reg2");
-    attr_done = true;
-  }
+  CRD_UNSUPPORTED(lds <= REG_GEMM_LDS_MAX, "crd_gn_conv2: table does not fit in LDS");
+  crd_reserve_lds_once<&k_gngemm_reg2<WM, WN, TM, TN, XF32, ACT>>(REG_GEMM_LDS_MAX, "k_gngemm_reg2");
   p.a0.lds_bytes = p.a1.lds_bytes = (int)tiles;
   hipLaunchKernelGGL((k_gngemm_reg2<WM, WN, TM, TN, XF32, ACT>), dim3(p.nb0 + nb1, B), dim3(256), lds, st, p);
   CRD_LAUNCH_CHECK("crd_gn_conv2");
@@ -287,16 +224,10 @@ int launch_reg(const ConvK& k0, GnIn gi, int B, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   ConvK k = k0;
   k.n_tiles = cdiv(k.OHW, BM);
-  size_t tiles = (size_t)2 * (BM + BN) * BK * 2;
-  if (tiles < epilogue_bytes<BM, BN>()) tiles = epilogue_bytes<BM, BN>();
-  tiles = (tiles + 255) / 256 * 256;
+  constexpr size_t tiles = reg_gemm_tile_bytes<BM, BN>();
   const size_t lds = tiles + (size_t)k.Cin * sizeof(float2);
-  CRD_UNSUPPORTED(lds <= 160 * 1024, "crd_gn_conv: table does not fit in LDS");
-  static bool attr_done = false;
-  if (!attr_done) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_gngemm_reg<WM, WN, TM, TN, XF32, ACT>), 160 * 1024, "k_gngemm_reg");
-    attr_done = true;
-  }
+  CRD_UNSUPPORTED(lds <= REG_GEMM_LDS_MAX, "crd_gn_conv: table does not fit in LDS");
+  crd_reserve_lds_once<&k_gngemm_reg<WM, WN, TM, TN, XF32, ACT>>(REG_GEMM_LDS_MAX, "k_gngemm_reg");
   k.lds_bytes = (int)tiles;
   hipLaunchKernelGGL((k_gngemm_reg<WM, WN, TM, TN, XF32, ACT>), dim3(k.n_tiles, cdiv(k.Cout, BN), B), dim3(256), lds, st, k, gi);
   CRD_LAUNCH_CHECK("crd_gn_conv");
@@ -342,7 +273,7 @@ __global__ __launch_bounds__(256, 2) void k_gn_pw_wide(ConvK a, GnIn gi, int ncb
   const int b = rest / R, s0 = rest - b * R;
   const int P = a.OHW, nT = (P + BM - 1) / BM;
   const int n0 = cb * NB + wv * WCT * 32;
-  const bool store_xn = gi.xn != nullptr && cb == 0;
+  const bool store_xn = gi.gn.xn != nullptr && cb == 0;
 
   // ---- everything the first tile needs is requested before anything is waited for: weights, the table's inputs, tile 0
   bf16x8 wf[WCT][KS];
@@ -392,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void k_gn_pw_wide(ConvK a, GnIn gi, int ncb
       q[1] = pack_bf2(v[2] * t1[0] + t1[1], v[3] * t1[2] + t1[3]);
       *reinterpret_cast<u32x2t*>(sA + (buf * BM + row) * LDA + g4 * 4) = q;
       const int p = tile * BM + row;
-      if (store_xn && p < P) *reinterpret_cast<u32x2t*>(gi.xn + (long long)b * gi.xn_bstride + (long long)p * gi.xn_ld + g4 * 4) = q;
+      if (store_xn && p < P) *reinterpret_cast<u32x2t*>(gi.gn.xn + (long long)b * gi.gn.xn_bstride + (long long)p * gi.gn.xn_ld + g4 * 4) = q;
     }
   };
   // invariant at the head of step(tile, P): sA[P] holds `tile`, xr(P^1) (in flight) tile + R, xr(P) tile + 2R.  One tile ahead was
@@ -575,7 +506,7 @@ bool pw_wide_applies(const ConvK& k, const GnIn& gi, int act_in) {
                      k.Cout % 128 == 0 && k.x_ld % 4 == 0;
   return on && shape && gi.x_f32 && act_in == 0 && !k.y_f32 && !k.res && !k.act && !k.accumulate && !k.chan && k.vec_ok &&
          (k.y_ld & 7) == 0 && (!k.bias || ((reinterpret_cast<uintptr_t>(k.bias) & 15) == 0 && k.bias_bstride % 4 == 0)) &&
-         (!gi.xn || gi.xn_ld % 4 == 0) && (reinterpret_cast<uintptr_t>(k.w) & 15) == 0;
+         (!gi.gn.xn || gi.gn.xn_ld % 4 == 0) && (reinterpret_cast<uintptr_t>(k.w) & 15) == 0;
 }
 
 template <int KS, int WCT, int XF, bool RED = false>
@@ -604,9 +535,7 @@ int dispatch_pw_wide(const ConvK& k, const GnIn& gi, int B, hipStream_t st) {
 
 template <int XF32, int ACT>
 int dispatch(const ConvK& k, const GnIn& gi, int B, hipStream_t st) {
-  // 64 x 64 tiles when 64 x 128 ones would not cover the chip (as crd_conv_igemm chooses)
-  const long long big_tiles = (long long)cdiv(k.OHW, 64) * cdiv(k.Cout, 128) * B;
-  if (k.Cout <= 64 || big_tiles < 256) return launch_reg<2, 2, 1, 1, XF32, ACT>(k, gi, B, st);
+  if (reg_gemm_small_tiles(k, B)) return launch_reg<2, 2, 1, 1, XF32, ACT>(k, gi, B, st);
   return launch_reg<2, 2, 1, 2, XF32, ACT>(k, gi, B, st);
 }
 
@@ -624,9 +553,7 @@ bool crd_pw_wide_plain_applicable(const ConvK& k) {
          (!k.bias || ((reinterpret_cast<uintptr_t>(k.bias) & 15) == 0 && k.bias_bstride % 4 == 0)) && (reinterpret_cast<uintptr_t>(k.w) & 15) == 0;
 }
 int crd_pw_wide_plain(const ConvK& k, int B, hipStream_t st) {
-  GnIn gi;
-  gi.x = k.x; gi.x_f32 = 0; gi.stats = nullptr; gi.gmul = 1; gi.gamma = nullptr; gi.beta = nullptr; gi.count = 1.f;
-  gi.xn = nullptr; gi.xn_ld = 0; gi.xn_bstride = 0;
+  const GnIn gi = {k.x, 0, NARROW_GN_NONE};
   if (k.red_x) {          // with the reduce phase of the following GroupNorm's backward in the epilogue (128-column workgroups)
                           // (correct -- tests/test_gpu_igemm.py runs it in a developer build -- but SLOWER in the step: 18.01 vs 17.91 ms;
                           //  the GELU' of 27-54 M elements costs more in this epilogue than the streaming reduce kernel it replaces)
@@ -650,34 +577,15 @@ static int gn_conv_args(const crd_conv_desc* d, const crd_gn_input* n, ConvK& k,
   CRD_UNSUPPORTED((long long)d->Cout * d->KH * d->KW * d->Cin < (1ll << 30) && d->Cin <= 4096 &&
                   (long long)d->IH * d->IW * d->x_ld * (n->x_f32 ? 4 : 2) < (1ll << 31), "crd_gn_conv: tensor too large for 32-bit byte offsets");
   CRD_CHECK_ARG(!n->xn || (n->xn_ld % 8 == 0 && (reinterpret_cast<uintptr_t>(n->xn) & 15) == 0), "crd_gn_conv: xn rows must be 16-byte aligned");
-  k.x = nullptr; k.x_ld = d->x_ld;
-  k.IH = d->IH; k.IW = d->IW; k.Cin = d->Cin; k.x_bstride = (long long)d->IH * d->IW * d->x_ld;
-  k.w = reinterpret_cast<const bf16_t*>(d->w);
-  k.Cout = d->Cout; k.KW = d->KW; k.stride = d->stride; k.pad = 0; k.Ktot = d->KH * d->KW * d->Cin;
-  k.OW = d->OW; k.OHW = d->OH * d->OW; k.gather_mode = 0;
-  k.y_ld = d->y_ld; k.y_f32 = d->y_f32;
-  k.out_mode = 0; k.patch_k = 0; k.patch_c = 0; k.YW = d->OW;
-  k.y_bstride = (long long)d->OH * d->OW * d->y_ld;
-  k.y = d->y_f32 ? (void*)(reinterpret_cast<float*>(d->y) + d->y_coff) : (void*)(reinterpret_cast<bf16_t*>(d->y) + d->y_coff);
-  k.bias = d->bias; k.bias_bstride = d->bias_bstride; k.act = d->act;
-  k.res = d->res; k.res_ld = d->res_ld; k.res_bstride = (long long)d->OH * d->OW * d->res_ld; k.res_scale = d->res_scale;
-  k.accumulate = d->accumulate; k.stats = d->stats; k.G16 = d->Cout / 16;
-  k.stats_partial = nullptr; k.n_tiles = 0; k.col0 = 0;
-  k.chan = d->chan_sums;
   CRD_UNSUPPORTED(!d->chan_sums || (d->stats && (d->y_f32 || d->res)), "crd_gn_conv: chan_sums needs stats and an fp32 / residual output");
-  k.vec_ok = (d->y_coff % 8 == 0) && ((reinterpret_cast<uintptr_t>(d->y) & 15) == 0);
-  k.vecf_ok = d->y_f32 && d->y_coff % 4 == 0 && d->y_ld % 4 == 0 && d->Cout % 4 == 0 && (reinterpret_cast<uintptr_t>(d->y) & 15) == 0 &&
-              (!d->res || (d->res_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(d->res) & 15) == 0));
-  k.lds_bytes = 0;
-  k.red_x = nullptr; k.red_x_f32 = 0; k.red_x_ld = 0; k.red_x_bstride = 0; k.red_stats = nullptr; k.red_gamma = nullptr; k.red_beta = nullptr;
-  k.red_gmul = 1; k.red_act = 0; k.red_r = nullptr;
-  { static int dbg = -1; if (dbg < 0) dbg = crd_dev_int("CRD_DBG", 0); k.dbg = dbg; }
+  convk_from_desc(*d, k);
+  k.x = nullptr;                       // the operand travels in gi: fp32 or bf16
   gi.x_f32 = n->x_f32;
   gi.x = n->x_f32 ? (const void*)(reinterpret_cast<const float*>(d->x) + d->x_coff) : (const void*)(reinterpret_cast<const bf16_t*>(d->x) + d->x_coff);
   CRD_CHECK_ARG((reinterpret_cast<uintptr_t>(gi.x) & 15) == 0 && (!n->x_f32 || d->x_ld % 4 == 0), "crd_gn_conv: x rows must be 16-byte aligned");
-  gi.stats = n->stats; gi.gmul = n->gmul; gi.gamma = n->gamma; gi.beta = n->beta;
-  gi.count = (float)d->IH * (float)d->IW * 16.f * (float)n->gmul;
-  gi.xn = reinterpret_cast<bf16_t*>(n->xn); gi.xn_ld = n->xn_ld; gi.xn_bstride = (long long)d->IH * d->IW * n->xn_ld;
+  gi.gn.stats = n->stats; gi.gn.gmul = n->gmul; gi.gn.gamma = n->gamma; gi.gn.beta = n->beta;
+  gi.gn.count = (float)d->IH * (float)d->IW * 16.f * (float)n->gmul;
+  gi.gn.xn = reinterpret_cast<bf16_t*>(n->xn); gi.gn.xn_ld = n->xn_ld; gi.gn.xn_bstride = (long long)d->IH * d->IW * n->xn_ld;
   return CRD_OK;
 }
 
@@ -689,10 +597,7 @@ extern "C" int crd_gn_conv(const crd_conv_desc* d, const crd_gn_input* n, crd_st
   if (n->act == 1 && !n->x_f32 && d->KH == 1) {        // Mlp.norm2 + GELU in front of fc2 at stages 1-2: the narrow streaming kernel
     ConvK kn = k;
     kn.x = reinterpret_cast<const bf16_t*>(gi.x);
-    NarrowGn ng;
-    ng.stats = gi.stats; ng.gmul = gi.gmul; ng.gamma = gi.gamma; ng.beta = gi.beta; ng.count = gi.count;
-    ng.xn = gi.xn; ng.xn_ld = gi.xn_ld; ng.xn_bstride = gi.xn_bstride;
-    if (crd_pw_narrow_applicable(kn, &ng)) return crd_pw_narrow(kn, &ng, d->B, st);
+    if (crd_pw_narrow_applicable(kn, &gi.gn)) return crd_pw_narrow(kn, &gi.gn, d->B, st);
   }
   if (pw_wide_applies(k, gi, n->act)) return dispatch_pw_wide<1>(k, gi, d->B, st);
   if (n->x_f32) return n->act ? dispatch<1, 1>(k, gi, d->B, st) : dispatch<1, 0>(k, gi, d->B, st);
@@ -707,7 +612,6 @@ extern "C" int crd_gn_conv2(const crd_conv_desc* d0, const crd_gn_input* n0, con
   CRD_UNSUPPORTED(d0->B == d1->B && n0->x_f32 == 1 && n1->x_f32 == 1 && n0->act == 0 && n1->act == 0,
                   "crd_gn_conv2: two problems of one batch behind a GroupNorm of the fp32 residual stream, no activation");
   // both on the 64 x 64 tiles (what crd_gn_conv picks for each of them alone at the encoder's sizes; a wide problem takes its own launch)
-  auto small = [&](const ConvK& k) { return k.Cout <= 64 || (long long)cdiv(k.OHW, 64) * cdiv(k.Cout, 128) * d0->B < 256; };
-  CRD_UNSUPPORTED(small(k0) && small(k1), "crd_gn_conv2: both problems must take the 64 x 64 tiles");
+  CRD_UNSUPPORTED(reg_gemm_small_tiles(k0, d0->B) && reg_gemm_small_tiles(k1, d0->B), "crd_gn_conv2: both problems must take the 64 x 64 tiles");
   return launch_reg2<2, 2, 1, 1, 1, 0>(k0, g0, k1, g1, d0->B, as_stream(stream));
 }

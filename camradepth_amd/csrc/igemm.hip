@@ -48,9 +48,6 @@ constexpr int BK = 64;                 // K elements per LDS stage (8 granules o
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 // MODE 0: forward gather (any stride); 1: data-gradient gather, stride 1; 2: data-gradient gather, strided
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // NST = LDS stages.  A K-slab of a 64x64 tile is only four MFMAs per wave, so with one slab in flight every K-step of
 // the small encoder GEMMs costs a full memory latency (12 us for K = 640); NST - 1 slabs in flight hide it.
 // KG > 1: intra-workgroup split-K.  KG groups of 4 waves each walk every KG-th K-slab with their own LDS stages and
@@ -259,11 +256,7 @@ template <int WM, int WN, int TM, int TN, int MODE, int NST, int KG = 1>
 void launch_mode(const ConvK& k, dim3 grid, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr size_t lds = (size_t)KG * NST * (BM + BN) * BK * sizeof(bf16_t);
-  static bool attr_done = false;
-  if (!attr_done && lds > 64 * 1024) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_igemm<WM, WN, TM, TN, MODE, NST, KG>), (int)lds, "k_igemm");
-    attr_done = true;
-  }
+  if (lds > 64 * 1024) crd_reserve_lds_once<&k_igemm<WM, WN, TM, TN, MODE, NST, KG>>((int)lds, "k_igemm");
   ConvK kk = k;
   kk.lds_bytes = (int)lds;
   if constexpr (TM == 1 && TN == 1 && KG == 1 && WM == 2 && WN == 2) {
@@ -305,36 +298,12 @@ extern "C" int crd_conv_igemm(const crd_conv_desc* d, crd_stream_t stream) {
                 "crd_conv_igemm: bad patch-scatter dims");
   CRD_UNSUPPORTED((long long)d->IH * d->IW * d->x_ld < (1ll << 30) && (long long)d->Cout * d->KH * d->KW * d->Cin < (1ll << 30),
                   "crd_conv_igemm: image or weight tensor too large for 32-bit byte offsets");
-  ConvK k;
-  k.x = reinterpret_cast<const bf16_t*>(d->x) + d->x_coff; k.x_ld = d->x_ld;
-  k.IH = d->IH; k.IW = d->IW; k.Cin = d->Cin; k.x_bstride = (long long)d->IH * d->IW * d->x_ld;
-  k.w = reinterpret_cast<const bf16_t*>(d->w);
-  k.Cout = d->Cout; k.KW = d->KW; k.stride = d->stride; k.pad = d->pad; k.Ktot = d->KH * d->KW * d->Cin;
-  k.OW = d->OW; k.OHW = d->OH * d->OW; k.gather_mode = d->gather_mode;
-  k.y_ld = d->y_ld; k.y_f32 = d->y_f32;
-  k.out_mode = d->out_mode; k.patch_k = d->patch_k; k.patch_c = d->patch_c;
-  int YH = d->OH, YW = d->OW;
-  if (d->out_mode == 1) { YH = d->OH * d->patch_k; YW = d->OW * d->patch_k; }
-  k.YW = YW;
-  k.y_bstride = (long long)YH * YW * d->y_ld;
-  k.y = d->y_f32 ? (void*)(reinterpret_cast<float*>(d->y) + d->y_coff) : (void*)(reinterpret_cast<bf16_t*>(d->y) + d->y_coff);
-  k.bias = d->bias; k.bias_bstride = d->bias_bstride; k.act = d->act;
-  k.res = d->res; k.res_ld = d->res_ld; k.res_bstride = (long long)YH * YW * d->res_ld; k.res_scale = d->res_scale;
-  k.accumulate = d->accumulate; k.stats = d->stats; k.G16 = d->Cout / 16;
-  k.stats_partial = d->stats ? d->stats_partial : nullptr; k.n_tiles = 0; k.col0 = 0;
-  k.chan = d->chan_sums;
   CRD_UNSUPPORTED(!d->chan_sums || (d->stats && (d->y_f32 || d->res || d->out_mode != 0)),
                   "crd_conv_igemm: chan_sums needs stats and an fp32 / residual output (the scalar epilogue)");
-  k.vec_ok = (d->y_coff % 8 == 0) && ((reinterpret_cast<uintptr_t>(d->y) & 15) == 0);
-  k.vecf_ok = d->y_f32 && d->y_coff % 4 == 0 && d->y_ld % 4 == 0 && d->Cout % 4 == 0 && (reinterpret_cast<uintptr_t>(d->y) & 15) == 0 &&
-              (!d->res || (d->res_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(d->res) & 15) == 0));
-  k.lds_bytes = 0;
-  k.red_x = d->red_x; k.red_x_f32 = d->red_x_f32; k.red_x_ld = d->red_x_ld;
-  k.red_x_bstride = (long long)YH * YW * d->red_x_ld;
-  k.red_stats = d->red_stats; k.red_gamma = d->red_gamma; k.red_beta = d->red_beta; k.red_gmul = d->red_gmul;
-  k.red_act = d->red_act; k.red_r = d->red_r;
+  ConvK k;
+  convk_from_desc(*d, k);
+  k.stats_partial = d->stats ? d->stats_partial : nullptr;       // per-tile partial sums only where there are sums
   const long long pcap = d->stats_partial ? d->stats_partial_capacity : 0;
-  { static int dbg = -1; if (dbg < 0) dbg = crd_dev_int("CRD_DBG", 0); k.dbg = dbg; }
   hipStream_t st = as_stream(stream);
   if (d->red_x) {
     const bool halo_shape = d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->IW >= 32 && d->IH >= 8;

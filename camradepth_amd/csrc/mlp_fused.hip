@@ -419,11 +419,7 @@ size_t mlp_lds_bytes(int N, int Cs) {
 // fit in 128 VGPRs next to the accumulators, and no stage of the model needs it)
 template <int NCH, int XIT>
 int mlp_launch(const MlpK& k, int slabs, size_t lds, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_mlp_fwd<NCH, XIT>), 160 * 1024, "k_mlp_fwd");
-    attr_done = true;
-  }
+  crd_reserve_lds_once<&k_mlp_fwd<NCH, XIT>>(160 * 1024, "k_mlp_fwd");
   hipLaunchKernelGGL((k_mlp_fwd<NCH, XIT>), dim3(slabs, k.B), dim3(MT), lds, st, k);
   return 0;
 }

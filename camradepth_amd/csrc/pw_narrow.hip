@@ -291,11 +291,10 @@ int launch_narrow(const ConvK& k, const NarrowGn* gn, int B, hipStream_t st) {
   constexpr int lds = lds_bytes<K, N, EPI>();
   static_assert(lds <= 160 * 1024, "LDS");
   static_assert(NWV * 64 * 16 * 4 + N * 2 * 4 + 64 <= 2 * RT * (K + 8) * 2, "the sum folds reuse the row buffers");
-  static bool attr_done = false;
-  if (!attr_done) { crd_reserve_lds(reinterpret_cast<const void*>(&k_pw_narrow<KS, NWV, XF, EPI>), lds, "k_pw_narrow"); attr_done = true; }
+  crd_reserve_lds_once<&k_pw_narrow<KS, NWV, XF, EPI>>(lds, "k_pw_narrow");
   NarrowArgs A;
   A.a = k;
-  if (gn) A.gn = *gn; else { A.gn.stats = nullptr; A.gn.gmul = 1; A.gn.gamma = A.gn.beta = nullptr; A.gn.count = 1.f; A.gn.xn = nullptr; A.gn.xn_ld = 0; A.gn.xn_bstride = 0; }
+  A.gn = gn ? *gn : NARROW_GN_NONE;
   A.tiles = k.OHW / RT;
   // workgroups: as many as stay resident (the LDS decides: one per CU at K = 1024, two at K = 512), balanced over a sample's tiles
   const int per_cu = (160 * 1024) / lds;

@@ -33,9 +33,6 @@ constexpr int XS = 6, YS = 4;                    // ring slots: input rows / dy 
 constexpr int XPX = 40;                          // pixels per staged input row (34 used, 5 DMA groups of 8)
 constexpr int XLD = 64;                          // channels per chunk (128-byte LDS rows)
 typedef __attribute__((address_space(3))) void* lds_ptr;
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // Source-side swizzle of the lane-linear LDS images so that the transposing reads are bank-conflict free: a 16-lane
 // group of ds_read_b64_tr_b16 fetches 4 pixel rows x 32 bytes, a half-wave two such groups 8 rows apart.  The 32-byte
 // unit u of row r is stored at unit u ^ f(r)  (found by exhaustive search over the access pattern; 64 banks x 4 B).
@@ -268,11 +265,7 @@ int launch_w3r(const Wg3K& k0, hipStream_t st, int budget, int partial_capacity)
   const size_t lds = (size_t)RPS * (XS * XPX * XLD + YS * 32 * COT) * sizeof(bf16_t);
   k.nchunks = cdiv(k.Cin, XLD);
   k.S = plan_rows(k.total_rows, k.Cin, k.rows_per_wg, budget, k.dw_part ? partial_capacity : 0);
-  static bool attr_done = false;
-  if (!attr_done) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_wgrad3x3<WCO, WCI, TCO, RPS>), (int)lds, "k_wgrad3x3");
-    attr_done = true;
-  }
+  crd_reserve_lds_once<&k_wgrad3x3<WCO, WCI, TCO, RPS>>((int)lds, "k_wgrad3x3");
   hipLaunchKernelGGL((k_wgrad3x3<WCO, WCI, TCO, RPS>), dim3(k.nchunks * k.S), dim3(512), lds, st, k);
   CRD_LAUNCH_CHECK("crd_conv_wgrad(3x3 streaming)");
   return CRD_OK;

@@ -10,7 +10,7 @@
 // attn.sr's patch scatter behind attn.norm) whose A rows can be produced on the fly from (dy, x) and the per-sample reduce sums.
 // Per block and GroupNorm this removes one launch from the dependency chain and one read of the gradient tensor.
 //
-// Structure = k_gngemm_reg: both operands by buffer_load to registers two K-steps ahead (dy AND the GroupNorm's input x for the A rows),
+// Structure = k_gngemm_reg, on the same skeleton (reg_gemm.h): both operands by buffer_load to registers two K-steps ahead (dy AND the GroupNorm's input x for the A rows),
 // transformed in registers on their way into a two-stage XOR-swizzled LDS tile; per-sample coefficient table in LDS:
 //   ACT 0:  dx = dy * ca + (x * cb + cc)                       ca = gamma mask rstd, cb = -rstd^2 S2, cc = -rstd S1 + mean rstd^2 S2
 //   ACT 1:  dx = dy * GELU'(x * za + zb) * ca + (x * cb + cc)   za = gamma rstd, zb = beta - mean za
@@ -18,13 +18,11 @@
 // (sums over the samples of r) are added by the workgroups of sample 0 / column tile 0, as crd_gn_bwd_apply does.
 // The epilogue (bias, accumulate, patch scatter, fused reduce of the NEXT GroupNorm's backward, GroupNorm sums) is conv_common.h's.
 #include <stdlib.h>
-#include "conv_common.h"
+#include "reg_gemm.h"
 
 using namespace crdk;
 
 namespace {
-
-constexpr int BK = 64;
 
 struct XfIn {
   const void* gx; int gx_f32; int gx_ld; long long gx_bstride;      // the GroupNorm's input [B][P][gx_ld] (bf16 or fp32)
@@ -66,36 +64,12 @@ __device__ __forceinline__ void build_table(const ConvK& a, const XfIn& xi, int 
   }
 }
 
-template <int TN>
-__device__ __forceinline__ void mfma_slab(const bf16_t* sa, const bf16_t* sb, f32x16 (&acc)[1][TN], int wm, int wn, int l) {
-#pragma unroll
-  for (int ks = 0; ks < BK / 16; ++ks) {
-    bf16x8 af, bfr[TN];
-    const int gi2 = ks * 2 + (l >> 5);
-    {
-      const int row = wm * 32 + (l & 31);
-      af = *reinterpret_cast<const bf16x8*>(&sa[row * BK + ((gi2 ^ ((row >> 1) & 7)) << 3)]);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = (wn * TN + j) * 32 + (l & 31);
-      bfr[j] = *reinterpret_cast<const bf16x8*>(&sb[row * BK + ((gi2 ^ ((row >> 1) & 7)) << 3)]);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[j], acc[0][j], 0, 0, 0);
-  }
-}
-
-template <int BM, int BN>
-constexpr size_t epilogue_bytes() { return (size_t)BM * (BN + 8) * 4 + 256 * 16 * 4 + 2048; }
-
 // 4 waves as 2 x 2, a 64 x (64 TN) tile per workgroup, one workgroup per (row tile, column tile, sample)
 template <int TN, int ACT, int GXF32>
 __global__ __launch_bounds__(256) void k_gnbwd_gemm(ConvK a, XfIn xi) {
   constexpr int WM = 2, WN = 2, TM = 1;
   constexpr int BM = 64, BN = WN * TN * 32;
   constexpr int A_IT = BM / 32, B_IT = BN / 32;
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4r;
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
   bf16_t* sA = lds;                                   // [2][BM][BK]   (the epilogue's staging area aliases the tiles)
   bf16_t* sB = sA + 2 * BM * BK;                      // [2][BN][BK]
@@ -119,15 +93,14 @@ __global__ __launch_bounds__(256) void k_gnbwd_gemm(ConvK a, XfIn xi) {
   const int by = ny ? (int)(blockIdx.x % (8 * ny)) >> 3 : (int)blockIdx.y;
   if (bx >= a.n_tiles) return;
   const int b = blockIdx.z, m0 = bx * BM, n0 = by * BN;
-  const int r0 = 8 * wv + (l >> 3);                   // this thread's rows: r0 + 32 i; LDS slot l & 7 <- K granule g (k_igemm's swizzle)
-  const int g = (l & 7) ^ ((r0 >> 1) & 7);
-  const unsigned OOB = 0x80000000u;
+  const RegLane ln = reg_lane(wv, l);
+  const int r0 = ln.r0, g = ln.g;                     // this thread's rows: r0 + 32 i; LDS slot l & 7 <- K granule g
   constexpr int esz = GXF32 ? 4 : 2;
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(a.x + (long long)b * a.x_bstride), 0, (int)(a.x_bstride * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(reinterpret_cast<const char*>(xi.gx) + (long long)b * xi.gx_bstride * esz), 0, (int)(xi.gx_bstride * esz), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.Cout * a.Ktot * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = reg_weight_rsrc(a);
   const __amdgpu_buffer_rsrc_t rdx = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(xi.dx ? xi.dx + (long long)b * xi.dx_bstride : reinterpret_cast<bf16_t*>(const_cast<void*>(xi.gx))), 0,
       xi.dx ? (int)(xi.dx_bstride * 2) : 0, 0x00020000);
@@ -135,10 +108,8 @@ __global__ __launch_bounds__(256) void k_gnbwd_gemm(ConvK a, XfIn xi) {
   const bool store_dx = xi.dx != nullptr && by == 0;
 
   // Loop-invariant BYTE offsets of this thread's rows in dy / x / dx, with the row's validity folded in (an invalid row starts at the
-  // out-of-range offset, and stays out of range whatever is added): every load and store of the K loop is then UNCONDITIONAL.  Written
-  // as `ok ? computed : OOB` inside the loop the compiler sank the multiply into a branch around the load -- two loads into the same
-  // registers on two exec-mask paths -- and, no longer able to count what was in flight, waited vmcnt(0) in front of every use: the
-  // two-slab prefetch was one slab deep (ISA of the first build; the conditional xn stores of k_gngemm_reg had the same effect).
+  // out-of-range offset, and stays out of range whatever is added): every load and store of the K loop is then UNCONDITIONAL
+  // (reg_gemm.h: THE K LOOP says why)
   unsigned dyoff[A_IT], gxoff[A_IT], dxoff[A_IT];
 #pragma unroll
   for (int i = 0; i < A_IT; ++i) {
@@ -149,11 +120,7 @@ __global__ __launch_bounds__(256) void k_gnbwd_gemm(ConvK a, XfIn xi) {
     dxoff[i] = (ok && store_dx) ? (unsigned)(m * xi.dx_ld * 2) : OOB;
   }
   unsigned woff[B_IT];
-#pragma unroll
-  for (int j = 0; j < B_IT; ++j) {
-    const int ng = n0 + r0 + 32 * j;
-    woff[j] = ng < a.Cout ? (unsigned)(ng * a.Ktot * 2) : OOB;
-  }
+  reg_weight_offsets(a, n0, r0, woff);
   struct Regs { u32x4r d[A_IT]; u32x4r x[A_IT][GXF32 ? 2 : 1]; u32x4r w[B_IT]; };
   auto load_slab = [&](int kt, Regs& r) {
     const int kc = kt * BK + g * 8;
@@ -165,9 +132,7 @@ __global__ __launch_bounds__(256) void k_gnbwd_gemm(ConvK a, XfIn xi) {
       r.x[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo, 0, 0);
       if (GXF32) r.x[i][GXF32 ? 1 : 0] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo + 16, 0, 0);
     }
-#pragma unroll
-    for (int j = 0; j < B_IT; ++j)
-      r.w[j] = __builtin_amdgcn_raw_buffer_load_b128(rw, (woff[j] + (unsigned)(kc * 2)) | km, 0, 0);
+    reg_load_weights(rw, woff, kc, km, r.w);
   };
   auto store_slab = [&](int kt, int stage, const Regs& r) {
     const int kc = kt * BK + g * 8;
@@ -226,35 +191,26 @@ __global__ __launch_bounds__(256) void k_gnbwd_gemm(ConvK a, XfIn xi) {
     }
   }
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = n0 + (wn * TN + j) * 32 + (l & 31);
-    const float bias_v = (a.bias && col < a.Cout) ? a.bias[(long long)b * a.bias_bstride + col] : 0.f;
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) acc[0][j][rr] = bias_v;
-  }
+  init_acc<TM, TN, WN>(a, acc, b, n0, wn, l);
+  // (four slabs in flight were tried: 256 registers or 36-92 spilled, one workgroup per CU -- not kept)
+  // the K loop: reg_gemm.h (THE K LOOP) has the rules -- no conditional memory operation in it -- and says why it is written out here
   lds_barrier();                                      // the table
   store_slab(0, 0, r0s);
   load_slab(2, r0s);
   lds_barrier();
-  // Steady state, two slabs per trip, NO conditional memory operation inside: a load or store under `if (kt + 3 < nK)` -- even a
-  // wave-uniform one -- makes the number of requests in flight path-dependent, and the compiler then waits as if the skipped path had
-  // been taken: every use drained the younger slab's requests as well (vmcnt(3..0) where vmcnt(8) was meant).  Slabs past the end carry
-  // out-of-range offsets instead (zeros in, nothing out), an odd slab count ends in a single-slab tail.  (Four slabs in flight were
-  // tried: 256 registers or 36-92 spilled, one workgroup per CU -- not kept.)
   int kt = 0;
   for (; kt + 2 <= nK; kt += 2) {
     store_slab(kt + 1, 1, r1s);
     load_slab(kt + 3, r1s);
-    mfma_slab<TN>(sA, sB, acc, wm, wn, l);
+    mfma_slab<TM, TN, WM, WN>(sA, sB, acc, wm, wn, l);
     lds_barrier();
     store_slab(kt + 2, 0, r0s);
     load_slab(kt + 4, r0s);
-    mfma_slab<TN>(sA + BM * BK, sB + BN * BK, acc, wm, wn, l);
+    mfma_slab<TM, TN, WM, WN>(sA + BM * BK, sB + BN * BK, acc, wm, wn, l);
     lds_barrier();
   }
   if (kt < nK) {
-    mfma_slab<TN>(sA, sB, acc, wm, wn, l);
+    mfma_slab<TM, TN, WM, WN>(sA, sB, acc, wm, wn, l);
     lds_barrier();
   }
   conv_epilogue<TM, TN, WM, WN>(a, acc, b, l, wm, wn, n0, bx, lds,
@@ -267,16 +223,10 @@ int launch(const ConvK& k0, const XfIn& xi, int B, hipStream_t st) {
   constexpr int BM = 64, BN = 64 * TN;
   ConvK k = k0;
   k.n_tiles = cdiv(k.OHW, BM);
-  size_t tiles = (size_t)2 * (BM + BN) * BK * 2;
-  if (tiles < epilogue_bytes<BM, BN>()) tiles = epilogue_bytes<BM, BN>();
-  tiles = (tiles + 255) / 256 * 256;
+  constexpr size_t tiles = reg_gemm_tile_bytes<BM, BN>();
   const size_t lds = tiles + (size_t)k.Cin * 20 + (size_t)(k.Cin / 16) * 16;
-  CRD_UNSUPPORTED(lds <= 160 * 1024, "crd_gn_bwd_conv: coefficient table does not fit in LDS");
-  static bool attr_done = false;
-  if (!attr_done) {
-    crd_reserve_lds(reinterpret_cast<const void*>(&k_gnbwd_gemm<TN, ACT, GXF32>), 160 * 1024, "k_gnbwd_gemm");
-    attr_done = true;
-  }
+  CRD_UNSUPPORTED(lds <= REG_GEMM_LDS_MAX, "crd_gn_bwd_conv: coefficient table does not fit in LDS");
+  crd_reserve_lds_once<&k_gnbwd_gemm<TN, ACT, GXF32>>(REG_GEMM_LDS_MAX, "k_gnbwd_gemm");
   k.lds_bytes = (int)tiles;
   const int ny = cdiv(k.Cout, BN);
   const bool xcd = ny >= 2 && k.n_tiles >= 7;
@@ -291,48 +241,12 @@ template <int ACT, int GXF32>
 int dispatch(const ConvK& k, const XfIn& xi, int B, hipStream_t st) {
   // 64-column tiles when 128-column ones would not cover the chip, and wherever the fused reduce of the epilogue needs threads that
   // keep their columns on a ragged last tile (crd_conv_igemm's rule: 64 < Cout <= 96 and 128 < Cout <= 160 have no 128-column form)
-  const long long big_tiles = (long long)cdiv(k.OHW, 64) * cdiv(k.Cout, 128) * B;
   const bool red_narrow = k.red_x && !((k.Cout > 96 && k.Cout <= 128) || k.Cout > 160);
-  if (k.Cout <= 64 || big_tiles < 256 || red_narrow || k.out_mode == 1) return launch<1, ACT, GXF32>(k, xi, B, st);
+  if (reg_gemm_small_tiles(k, B) || red_narrow || k.out_mode == 1) return launch<1, ACT, GXF32>(k, xi, B, st);
   return launch<2, ACT, GXF32>(k, xi, B, st);
 }
 
 }  // namespace
-
-// ConvK of a pointwise data-gradient GEMM from the descriptor
-static int fill_convk(const crd_conv_desc* d, ConvK& k, const char* who) {
-  k.x = reinterpret_cast<const bf16_t*>(d->x) + d->x_coff; k.x_ld = d->x_ld;
-  k.IH = d->IH; k.IW = d->IW; k.Cin = d->Cin; k.x_bstride = (long long)d->IH * d->IW * d->x_ld;
-  k.w = reinterpret_cast<const bf16_t*>(d->w);
-  k.Cout = d->Cout; k.KW = 1; k.stride = 1; k.pad = 0; k.Ktot = d->Cin;
-  k.OW = d->OW; k.OHW = d->OH * d->OW; k.gather_mode = 0;
-  k.y_ld = d->y_ld; k.y_f32 = 0;
-  k.out_mode = d->out_mode; k.patch_k = d->patch_k; k.patch_c = d->patch_c;
-  int YH = d->OH, YW = d->OW;
-  if (d->out_mode == 1) { YH = d->OH * d->patch_k; YW = d->OW * d->patch_k; }
-  k.YW = YW;
-  k.y_bstride = (long long)YH * YW * d->y_ld;
-  k.y = (void*)(reinterpret_cast<bf16_t*>(d->y) + d->y_coff);
-  k.bias = d->bias; k.bias_bstride = d->bias_bstride; k.act = 0;
-  k.res = nullptr; k.res_ld = 0; k.res_bstride = 0; k.res_scale = nullptr;
-  k.accumulate = d->accumulate; k.stats = d->stats; k.G16 = d->Cout / 16;
-  k.stats_partial = nullptr; k.n_tiles = 0; k.col0 = 0; k.chan = nullptr;
-  k.vec_ok = (d->y_coff % 8 == 0) && ((reinterpret_cast<uintptr_t>(d->y) & 15) == 0);
-  k.vecf_ok = 0;
-  k.lds_bytes = 0;
-  k.red_x = d->red_x; k.red_x_f32 = d->red_x_f32; k.red_x_ld = d->red_x_ld;
-  k.red_x_bstride = (long long)YH * YW * d->red_x_ld;
-  k.red_stats = d->red_stats; k.red_gamma = d->red_gamma; k.red_beta = d->red_beta; k.red_gmul = d->red_gmul;
-  k.red_act = d->red_act; k.red_r = d->red_r;
-  k.dbg = 0;
-  if (d->red_x) {
-    CRD_CHECK_ARG(d->red_stats && d->red_gamma && d->red_beta && d->red_r && d->red_gmul >= 1 && d->red_x_ld % 8 == 0 &&
-                  (d->Cout / 16) % d->red_gmul == 0, "%s: incomplete fused-reduce arguments", who);
-    CRD_UNSUPPORTED(d->Cout % 16 == 0 && d->out_mode == 0 && d->y_ld % 8 == 0 && k.vec_ok,
-                    "%s: the fused GroupNorm-backward reduce needs a plain-layout bf16 vector-path output", who);
-  }
-  return CRD_OK;
-}
 
 extern "C" int crd_gn_bwd_conv(const crd_conv_desc* d, const crd_gn_bwd_input* n, crd_stream_t stream) {
   CRD_CHECK_ARG(d && n && d->x && d->w && d->y && n->gx && n->stats && n->gamma && n->beta && n->r, "crd_gn_bwd_conv: null pointer");
@@ -352,7 +266,14 @@ extern "C" int crd_gn_bwd_conv(const crd_conv_desc* d, const crd_gn_bwd_input* n
   CRD_UNSUPPORTED((long long)d->Cout * d->Cin < (1ll << 30) && d->Cin <= 4096 && (long long)d->IH * d->IW * d->x_ld * 2 < (1ll << 31) &&
                   (long long)d->IH * d->IW * n->gx_ld * (n->gx_f32 ? 4 : 2) < (1ll << 31), "crd_gn_bwd_conv: tensor too large for 32-bit byte offsets");
   ConvK k;
-  { const int rc = fill_convk(d, k, "crd_gn_bwd_conv"); if (rc != CRD_OK) return rc; }
+  convk_from_desc(*d, k);
+  k.gather_mode = 0;          // whatever the descriptor says: the engine passes gather = 1 for data gradients, a pointwise GEMM has no taps to flip
+  if (d->red_x) {
+    CRD_CHECK_ARG(d->red_stats && d->red_gamma && d->red_beta && d->red_r && d->red_gmul >= 1 && d->red_x_ld % 8 == 0 &&
+                  (d->Cout / 16) % d->red_gmul == 0, "crd_gn_bwd_conv: incomplete fused-reduce arguments");
+    CRD_UNSUPPORTED(d->Cout % 16 == 0 && d->out_mode == 0 && d->y_ld % 8 == 0 && k.vec_ok,
+                    "crd_gn_bwd_conv: the fused GroupNorm-backward reduce needs a plain-layout bf16 vector-path output");
+  }
   CRD_CHECK_ARG((reinterpret_cast<uintptr_t>(k.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(n->gx) & 15) == 0 && (!n->gx_f32 || n->gx_ld % 4 == 0),
                 "crd_gn_bwd_conv: dy / x rows must be 16-byte aligned");
   XfIn xi;

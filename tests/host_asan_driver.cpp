@@ -36,6 +36,23 @@ int main() {
   printf("null dgn: %d (%s)\n", crd_diffgradnorm_step(nullptr, nullptr), crd_last_error());
   crd_dgn_desc z; memset(&z, 0, sizeof z);
   printf("zeroed dgn: %d (%s)\n", crd_diffgradnorm_step(&z, nullptr), crd_last_error());
+  // refusals behind the kernel argument block: the descriptor passes the first checks, the block is built from it, a later check refuses
+  alignas(16) static char buf[64];
+  crd_conv_desc c; memset(&c, 0, sizeof c);
+  c.x = c.w = c.y = buf; c.B = 1; c.IH = c.IW = c.OH = c.OW = 8; c.Cin = c.x_ld = c.Cout = c.y_ld = 64; c.KH = c.KW = c.stride = 1;
+  crd_conv_desc r = c;
+  r.red_x = buf;
+  printf("igemm incomplete reduce: %d (%s)\n", crd_conv_igemm(&r, nullptr), crd_last_error());
+  crd_gn_input gn; memset(&gn, 0, sizeof gn);
+  gn.stats = (const crd_sum_t*)buf; gn.gamma = gn.beta = (const float*)buf; gn.gmul = 1;
+  crd_conv_desc m = c;
+  m.x = buf + 8;
+  printf("gn_conv misaligned x: %d (%s)\n", crd_gn_conv(&m, &gn, nullptr), crd_last_error());
+  crd_gn_bwd_input gb; memset(&gb, 0, sizeof gb);
+  gb.gx = buf; gb.gx_ld = 64; gb.gmul = 1; gb.stats = (const crd_sum_t*)buf; gb.gamma = gb.beta = (const float*)buf; gb.r = (const crd_sum_t*)buf;
+  r.red_stats = (const crd_sum_t*)buf; r.red_gamma = r.red_beta = (const float*)buf; r.red_r = (crd_sum_t*)buf; r.red_gmul = 1; r.red_x_ld = 64;
+  r.y_coff = 4;
+  printf("gn_bwd_conv reduce off the vector path: %d (%s)\n", crd_gn_bwd_conv(&r, &gb, nullptr), crd_last_error());
   printf("version %d arch %s\n", crd_version(), crd_arch());
   return 0;
 }

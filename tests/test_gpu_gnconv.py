@@ -51,6 +51,11 @@ CASES = [
     (8, 1024, 32, 52, 128, 1, 8, 1, 0, "res"),            # fc2 stage 2 at the benchmark size: the narrow streaming kernel (round 5), 2 tiles per workgroup
     (3, 1024, 8, 12, 128, 1, 8, 1, 0, "res"),             # ... three tiles per sample, odd batch
     (2, 512, 16, 24, 64, 1, 8, 1, 0, "plain"),            # ... its bf16-output form behind GroupNorm + GELU
+    # the register path's K loop (two 64-channel slabs per trip) on one 8 x 8 row tile:
+    (2, 80, 8, 8, 64, 1, 1, 0, 1, "plain"),               # K = 80: the K tail inside the second slab
+    (2, 192, 8, 8, 64, 1, 1, 0, 0, "stats"),              # K = 192: odd slab count, single-slab tail
+    (2, 128, 8, 8, 96, 1, 1, 0, 1, "plain"),              # K = 128: even slab count, ragged columns
+    (2, 64, 16, 24, 64, 1, 1, 0, 1, "noxn"),              # plain output, the normalised operand NOT stored
 ]
 
 
@@ -86,7 +91,8 @@ def test_gn_conv_matches_groupnorm_then_conv(case):
     n.x_f32, n.gmul, n.act = x_f32, gmul, act
     gam_d, bet_d = gamma.cuda(), beta.cuda()
     n.stats, n.gamma, n.beta = stats.data_ptr(), gam_d.data_ptr(), bet_d.data_ptr()
-    n.xn, n.xn_ld = xn_out.data_ptr(), Cin
+    if epi != "noxn":
+        n.xn, n.xn_ld = xn_out.data_ptr(), Cin
     ostats = zsum(B, Cout // 16, 2)
     if epi == "res":
         y = torch.zeros(B, OH * OW, Cout, device="cuda")
@@ -114,7 +120,10 @@ def test_gn_conv_matches_groupnorm_then_conv(case):
     # the normalised operand is stored for the weight gradient: bf16 of the torch value, up to one ulp where the fp32
     # statistics (sum / sum of squares here, two-pass in torch) move a value across a rounding boundary
     xn_ref = xn_b.permute(0, 2, 3, 1).reshape(B, H * W, Cin)
-    assert_close(xn_out.float().cpu(), xn_ref, "stored normalised operand", rel=3e-3, elem=1.6e-2)
+    if epi == "noxn":
+        assert not bool(xn_out.any()), "nothing is stored without xn"
+    else:
+        assert_close(xn_out.float().cpu(), xn_ref, "stored normalised operand", rel=3e-3, elem=1.6e-2)
     if epi in ("stats", "res"):
         stored = y.float().cpu().reshape(B, OH * OW, Cout).permute(0, 2, 1).reshape(B, Cout, OH, OW)
         assert_close(sval(ostats), slab_sums(stored), "output GroupNorm sums", rel=2e-3, elem=5e-3)
@@ -155,6 +164,12 @@ BWD_CASES = [
     (2, 512, 12, 20, 64, 8, 1, 0, "plain"),      # Mlp.norm2 + GELU (groups of 8 slabs)
     (2, 64, 9, 11, 512, 1, 0, 1, "plain"),       # fp32 GroupNorm input (the residual stream), 128-wide column tiles
     (8, 160, 16, 26, 640, 1, 0, 1, "stats"),     # ... with output sums
+    # the K loop (two 64-channel slabs per trip) on one 8 x 8 row tile of the plain grid:
+    (2, 80, 8, 8, 64, 1, 0, 0, "plain"),         # K = 80: the K tail inside the second slab
+    (2, 192, 8, 8, 64, 1, 0, 1, "plain"),        # K = 192: odd slab count, single-slab tail
+    (2, 128, 8, 8, 64, 1, 0, 0, "nodx"),         # K = 128: even slab count; dx NOT stored
+    (2, 64, 16, 32, 256, 1, 0, 0, "plain"),      # eight row tiles x four 64-column tiles: the XCD-ordered 1-D grid
+    (2, 64, 64, 64, 256, 1, 0, 0, "plain"),      # 64 row tiles: the 128-column tile
 ]
 
 
@@ -235,12 +250,17 @@ def test_gn_bwd_conv_matches_apply_then_conv(case):
     dx1 = torch.zeros(B, P, Ci, dtype=torch.bfloat16, device="cuda")
     n.gx, n.gx_f32, n.gx_ld, n.gmul, n.act = xpm.data_ptr(), gxf32, Ci, gmul, act
     n.stats, n.gamma, n.beta, n.r = stats.data_ptr(), gam_d.data_ptr(), bet_d.data_ptr(), r.data_ptr()
-    n.dx, n.dx_ld, n.dgamma, n.dbeta = dx1.data_ptr(), Ci, dga1.data_ptr(), dbe1.data_ptr()
+    n.dgamma, n.dbeta = dga1.data_ptr(), dbe1.data_ptr()
+    if mode != "nodx":
+        n.dx, n.dx_ld = dx1.data_ptr(), Ci
     lib.check(L.crd_gn_bwd_conv(C.byref(d), C.byref(n), lib.stream()), "crd_gn_bwd_conv")
     torch.cuda.synchronize()
     # stored gradient: the apply kernel's, up to one bf16 ulp where the fp32 evaluation order moves a value across a rounding boundary
-    assert_close(dx1.float().cpu(), dx0.float().cpu(), "stored dx vs crd_gn_bwd_apply", rel=2e-3, elem=1.6e-2)
-    assert_close(dx1.float().cpu().reshape(B, H, W, Ci).permute(0, 3, 1, 2), dx_ref, "stored dx vs autograd", rel=6e-3, elem=2e-2)
+    if mode == "nodx":
+        assert not bool(dx1.any()), "nothing is stored without dx"
+    else:
+        assert_close(dx1.float().cpu(), dx0.float().cpu(), "stored dx vs crd_gn_bwd_apply", rel=2e-3, elem=1.6e-2)
+        assert_close(dx1.float().cpu().reshape(B, H, W, Ci).permute(0, 3, 1, 2), dx_ref, "stored dx vs autograd", rel=6e-3, elem=2e-2)
     assert torch.equal(dga0, dga1) and torch.equal(dbe0, dbe1)
     assert_close(y1.float().cpu(), y0.float().cpu(), "product vs apply + conv_igemm", rel=4e-3, elem=1.5e-2)
     # against torch: conv of the bf16-rounded autograd gradient

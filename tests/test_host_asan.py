@@ -44,5 +44,8 @@ def test_host_code_is_asan_clean():
         assert r.returncode == 0 and "AddressSanitizer" not in out, out[-4000:]
         assert "build rc 0" in out and "short table rc -1" in out and "splits(cap 12) = 12" in out and "null conv: -1" in out, out
         assert "null dgn: -1" in out and "zeroed dgn: -1" in out, out
+        assert "igemm incomplete reduce: -1 (crd_conv_igemm: incomplete fused-reduce arguments)" in out, out
+        assert "gn_conv misaligned x: -1 (crd_gn_conv: x rows must be 16-byte aligned)" in out, out
+        assert "gn_bwd_conv reduce off the vector path: -2 (crd_gn_bwd_conv: the fused GroupNorm-backward reduce needs" in out, out
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
