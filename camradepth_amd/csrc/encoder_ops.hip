@@ -1118,17 +1118,28 @@ extern "C" int crd_attn_out_residual(const float* x, const float* u, const float
   return CRD_OK;
 }
 
-static int attn_out_bwd_launch(float* dx1, const float* u, const float* S, const float* dp, int32_t B, int32_t N, int32_t C, crd_sum_t* t,
-                               crd_sum_t* dbp_rows, float* dS, const GnPre* pre, const char* who, crd_stream_t stream) {
-  CRD_CHECK_ARG(dx1 && u && S && t && dbp_rows && dS, "%s: null pointer", who);
-  CRD_UNSUPPORTED(C % 8 == 0 && C <= 512, "%s: C must be a multiple of 8 and <= 512", who);
+// workgroups per sample of k_attn_out_bwd: 256 pixels each, fewer on small grids, at most 1024 workgroups per launch
+static int attn_out_bwd_blocks(int B, int N) {
   static int small = -1;
   if (small < 0) small = crd_dev_int("CRD_ATTN_OUT_BWD_CHUNK", 32);
   int nblk = cdiv(N, (long long)B * cdiv(N, 256) < 128 ? small : 256);     // fewer pixels per workgroup on small grids
   int cap = 1024 / (B > 0 ? B : 1); if (cap < 1) cap = 1;
   if (nblk > cap) nblk = cap;
-  int chunk = cdiv(N, nblk);
-  nblk = cdiv(N, chunk);
+  const int chunk = cdiv(N, nblk);
+  return cdiv(N, chunk);
+}
+
+extern "C" int crd_attn_out_bwd_blocks(int32_t B, int32_t N, int32_t C) {
+  (void)C;                                 // the rule does not depend on the channel count (the lanes per pixel do, inside the kernel)
+  return B > 0 && N > 0 ? attn_out_bwd_blocks(B, N) : 0;
+}
+
+static int attn_out_bwd_launch(float* dx1, const float* u, const float* S, const float* dp, int32_t B, int32_t N, int32_t C, crd_sum_t* t,
+                               crd_sum_t* dbp_rows, float* dS, const GnPre* pre, const char* who, crd_stream_t stream) {
+  CRD_CHECK_ARG(dx1 && u && S && t && dbp_rows && dS, "%s: null pointer", who);
+  CRD_UNSUPPORTED(C % 8 == 0 && C <= 512, "%s: C must be a multiple of 8 and <= 512", who);
+  const int nblk = attn_out_bwd_blocks(B, N);
+  const int chunk = cdiv(N, nblk);
   if (pre) hipLaunchKernelGGL(k_attn_out_bwd<true>, dim3(nblk, B), dim3(TPB), 2 * C * sizeof(float), as_stream(stream), dx1, u, S, dp,
                               (long long)N, C, chunk, t, dbp_rows, dS, *pre);
   else hipLaunchKernelGGL(k_attn_out_bwd<false>, dim3(nblk, B), dim3(TPB), 2 * C * sizeof(float), as_stream(stream), dx1, u, S, dp,

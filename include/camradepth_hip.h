@@ -439,6 +439,10 @@ int crd_attn_out_bwd(const float* dx1, const float* u, const float* S, const flo
 int crd_attn_out_bwd_gn(float* dx1, const float* u, const float* S, const float* dp, int32_t B, int32_t N, int32_t C,
                         crd_sum_t* t, crd_sum_t* dbp_rows, float* dS, const float* x, const void* dxn, const crd_sum_t* stats,
                         const float* gamma, const crd_sum_t* r, float* dgamma, float* dbeta, crd_stream_t stream);
+/* Workgroups per sample of crd_attn_out_bwd / crd_attn_out_bwd_gn at this problem size (each takes ceil(N / that many)
+ * consecutive pixels); 0 for B or N < 1.  Host arithmetic only, as crd_attn_scores_bwd_partials: the launchers use the same
+ * rule, and the tests pin through it which geometry a shape runs.  A new entry, no changed signature: CRD_ABI_VERSION stays. */
+int crd_attn_out_bwd_blocks(int32_t B, int32_t N, int32_t C);
 /* dq[b][n][c] = scale*dS[b][n]*k[b][idx][c] (bf16) ; dk[b][m][c] += scale*dS*q (caller zeroes).
  * Every workgroup accumulates its share of dk in LDS (when [M][C] fp32 fits: always at the reference's sizes).  With
  * dk_partials != NULL (float [P][B][M][C], P = crd_attn_scores_bwd_partials(B,N,M,heads,d) > 0; contents don't-care)
