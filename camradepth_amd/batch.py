@@ -1,7 +1,9 @@
 """GPU-side batch assembly: the tensor contract of the reference dataloader (src/data/dataloader.py:202-333) for the
 radar configuration -- 7-channel input, inverse-normalised LiDAR ground truth and its zero-ignoring min-pool pyramid --
 from raw device buffers (uint8 image as cv2 reads it, radar [H,W,3], radial velocity, LiDAR depth in metres).  File
-decoding, the nearest-neighbour image resize and the segmentation resize stay on the host (no cv2 / skimage here).
+decoding stays on the host; the image, the radar maps and the ground truth have device front ends of their own
+(camradepth_amd.camera, .radar, .lidar), and the nearest-neighbour resizes of images and label maps are resize_image_nearest
+and seg_targets below (no cv2 / skimage here).
 
 Augmentation (`Augment`: random crop, horizontal flip, photometric jitter of the image) is this project's own -- the reference
 trains without any -- and off unless asked for: INTEGRATION.md, "Augmentation"."""

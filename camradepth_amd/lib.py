@@ -156,6 +156,7 @@ _SIGS = {
     "crd_lidar_project": "pppiippppippipppipiiiffLLpppppppppp", "crd_lidar_ground_truth": "pppppppppiipiiiiipppipLplpppp",
     "crd_depth_unproject": "piiiiipipiiLLLipppppp", "crd_point_cloud": "piiiiipipiiLLLipppipplpppppp",
     "crd_viz_range": "piiiiipplpp", "crd_viz_draw": "piiiippffipiiffipllp", "crd_seg_labels": "piiiipp",
+    "crd_camera_frontend": "piiiilliiippip",
     "crd_resize_nearest_u8":"piiiipiip", "crd_resize_labels_nearest": "piiiipiip", "crd_seg_confusion": "ppiilppp",
     "crd_masked_l1_fwd": "pplpp", "crd_test_metrics": "ppilffpp", "crd_depth_eval": "ppilfffipp", "crd_masked_l1_bwd": "pplppfpp", "crd_ce_fwd": "ppiilpp",
     "crd_ce_focal_bwd": "ppiilppfpp",

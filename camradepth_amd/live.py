@@ -1,0 +1,204 @@
+"""Raw sensors to depth, point cloud and pictures in ONE captured graph: the camera front end, the radar front end, the input
+assembly, the eval-mode network, the point-cloud back end and the visualiser on static buffers, replayed once per frame.
+
+Each stage exists on its own (camera.camera_inputs, radar.radar_inputs, batch.assemble_batch, inference.InferenceGraph,
+cloud.point_cloud, viz.Visualizer) and LivePipeline.run returns the bits of calling them one by one; what it adds is the ownership of
+every buffer between sensor and picture and one replay in place of a host call per stage: INTEGRATION.md, "Live pipeline".  The lidar
+ground-truth front end serves training and is not part of it.  Nothing calls this module unless asked."""
+import math
+
+import torch
+
+from . import lib as L
+from .camera import ORDERS, camera_inputs
+from .cloud import CloudWorkspace, point_cloud
+from .radar import RadarWorkspace, radar_inputs
+from ._frontend import _size, map_shape
+from .viz import Visualizer
+
+CLOUD_OPTIONS = {"stride": 1, "min_range": 0.0, "max_range": math.inf, "max_depth": 100.0, "rgb": False, "pixel": False}
+RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
+
+
+def _copies(v):
+    if torch.is_tensor(v):
+        return v.clone()
+    if isinstance(v, dict):
+        return {k: _copies(t) for k, t in v.items()}
+    if isinstance(v, tuple):
+        return tuple(_copies(t) for t in v)
+    return v
+
+
+class LivePipeline:
+    """model.eval() on raw sensor data for a fixed batch of B frames of image_size pixels, captured once on one stream.
+
+    model: a CamRaDepth on the device with input_channels 7 (image, radar depth, radar flow, radial velocity), 6 (without the radial
+    velocity) or 3 (RGB only: run() then takes no radar arguments and the camera kernel writes the network input directly).
+    (h, w) = map_shape(image_size, downsample_scale, y_cutoff) must be a shape the network takes (multiples of 32).  max_points and
+    max_sweeps: the capacity of the radar tables (every run may bring fewer).  frame_channels, order_in: the raw frames' bytes per
+    pixel (3 or 4) and channel order; order_out: the order the network was trained on ('bgr', as cv2 reads).  max_depth, min_distance,
+    min_z: as for assemble_batch and radar_inputs.
+    cloud: None, or a dictionary of point_cloud's stride, min_range, max_range, max_depth, rgb (colours from the image) and pixel.
+    viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
+
+    The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
+    plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
+    point_cloud, Visualizer.render."""
+
+    def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
+                 frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None):
+        fn = "LivePipeline"
+        if model.flat is None or not model.flat.is_cuda:
+            raise L.CrdError(f"{fn} needs the model on an MI355X (no CPU fallback)")
+        Cin = model.cfg.input_channels
+        if Cin not in (3, 6, 7):
+            raise L.CrdError(f"{fn}: a model of {Cin} input channels; 7, 6 (image and radar) or 3 (image only) are assembled here")
+        if order_in not in ORDERS or order_out not in ORDERS:
+            raise L.CrdError(f"{fn}: order_in and order_out are 'rgb' or 'bgr', not {order_in!r} and {order_out!r}")
+        if frame_channels not in (3, 4) or int(B) <= 0:
+            raise L.CrdError(f"{fn}: B {B}, frame_channels {frame_channels} (3 or 4)")
+        h, w = map_shape(image_size, downsample_scale, y_cutoff)
+        if h % 32 or w % 32:
+            raise L.CrdError(f"{fn}: image {tuple(image_size)}, downsample_scale {downsample_scale}, y_cutoff {y_cutoff} give maps of "
+                             f"{h} x {w}; the network takes multiples of 32")
+        self.radar_on = Cin > 3
+        if self.radar_on and (max_points is None or max_sweeps is None or int(max_points) <= 0 or int(max_sweeps) <= 0):
+            raise L.CrdError(f"{fn}: a model with radar channels needs max_points and max_sweeps, the capacity of the radar tables")
+        if cloud is not None and not set(cloud) <= set(CLOUD_OPTIONS):
+            raise L.CrdError(f"{fn}: cloud= holds {sorted(CLOUD_OPTIONS)}, not {sorted(set(cloud) - set(CLOUD_OPTIONS))}")
+        dev = model.flat.device
+        self.model, self.B, self.h, self.w = model, int(B), h, w
+        self.image_size, self.downsample_scale, self.y_cutoff = _size(image_size), int(downsample_scale), int(y_cutoff)
+        self.order_in, self.order_out, self.max_depth = order_in, order_out, float(max_depth)
+        self.min_distance, self.min_z = float(min_distance), float(min_z)
+        H, W = self.image_size
+        B = self.B
+        # every static buffer between sensor and picture
+        self.frames = torch.zeros(B, H, W, int(frame_channels), dtype=torch.uint8, device=dev)
+        self.image = torch.empty(B, h, w, 3, dtype=torch.uint8, device=dev)
+        self.K = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1)
+        self.camera_frame = torch.eye(3, 4, dtype=torch.float64, device=dev).repeat(B, 1, 1)       # out_from_cam=None: (I | 0)
+        self.out_from_cam = self.camera_frame.clone()
+        if self.radar_on:
+            N, S = int(max_points), int(max_sweeps)
+            self.max_points, self.max_sweeps = N, S
+            self.points = torch.zeros(N, 5, dtype=torch.float64, device=dev)
+            self.sweep_index = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.frame_offsets = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+            self.cam1_from_sensor = torch.zeros(S, 3, 4, dtype=torch.float64, device=dev)
+            self.cam2_from_sensor = torch.zeros(S, 3, 4, dtype=torch.float64, device=dev)
+            self.lags = torch.zeros(S, 2, dtype=torch.float64, device=dev)
+            self.radar_ws = RadarWorkspace(B, self.image_size, self.downsample_scale, max_points=N, device=dev)
+            self.radar_out = {"radar": torch.empty(B, h, w, 3, device=dev), "rad_vel": torch.empty(B, h, w, device=dev)}
+        self.cloud_opts = None if cloud is None else dict(CLOUD_OPTIONS, **cloud)
+        if self.cloud_opts is not None:
+            self.cloud_ws = CloudWorkspace(B, self.image_size, self.downsample_scale, self.y_cutoff, self.cloud_opts["stride"], device=dev)
+            self.cloud_out = self.cloud_ws.outputs(rgb=bool(self.cloud_opts["rgb"]), pixel=bool(self.cloud_opts["pixel"]))
+        self.visualizer = None if viz is None else Visualizer(B, h, w, **dict({"image_order": order_out, "device": dev}, **viz))
+        # the eval plan, exactly as InferenceGraph takes it
+        was_training = model.training
+        model.eval()
+        prev = model.__dict__.get("_need_grad", True)
+        model.__dict__["_need_grad"] = False        # inference: nothing is kept for a backward pass
+        try:
+            self.plan = model._plan_for(torch.zeros((B, Cin, h, w), device=dev))
+        finally:
+            model.__dict__["_need_grad"] = prev     # (part of the plan key: a later model._plan_for() must not inherit it)
+        self.stream = torch.cuda.Stream()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self._stages(pack=True)                 # warm-up outside the capture (lazy module loading)
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=self.stream):
+                self._results = self._stages(pack=False)
+        torch.cuda.current_stream().wait_stream(self.stream)
+        model.train(was_training)
+
+    def _pred(self):
+        """The reference's nested output dictionary as views of the plan's static buffers (InferenceGraph.run(clone=False))."""
+        p, B, H, W = self.plan, self.B, self.h, self.w
+        final = p.out_depth[5].t.view(B, 1, H, W)
+        half = p.out_depth[4].t.view(B, 1, H // 2, W // 2)
+        quarter = p.out_depth[3].t.view(B, 1, H // 4, W // 4)
+        return {"depth": {"intermediate_depths": (None, None, quarter, half), "final_depth": final},
+                "seg": {"final_seg": p.seg_out if p.seg_logits is not None else None, "intermediate_seg": None, "unsup_map": p.unsup_map}}
+
+    def _stages(self, pack):
+        """The whole chain on the current stream, every stage writing into this object's buffers -> the dictionary run() returns."""
+        p, s, cut = self.plan, self.downsample_scale, self.y_cutoff
+        out = {"x": p.x_in}
+        if self.radar_on:
+            out["image"] = camera_inputs(self.frames, s, cut, self.order_in, self.order_out, out={"image": self.image})["image"]
+            maps = radar_inputs(self.points, self.sweep_index, self.frame_offsets, self.cam1_from_sensor, self.cam2_from_sensor, self.lags,
+                                self.K, self.image_size, self.min_distance, self.min_z, s, cut, workspace=self.radar_ws, out=self.radar_out)
+            rad_vel = maps["rad_vel"] if p.x_in.shape[1] == 7 else None
+            L.check(p.lib.crd_assemble_input(L.ptr(self.image), L.ptr(maps["radar"]), L.ptr(rad_vel), self.B, self.h, self.w, self.max_depth,
+                                             L.ptr(p.x_in), L.stream()), "crd_assemble_input")
+            out.update(radar=maps["radar"], rad_vel=maps["rad_vel"])
+        else:
+            out["image"] = camera_inputs(self.frames, s, cut, self.order_in, self.order_out, out={"image": self.image, "x": p.x_in})["image"]
+        p.forward(pack=pack)
+        pred = out["pred"] = self._pred()
+        if self.cloud_opts is not None:
+            o = self.cloud_opts
+            out["cloud"] = point_cloud(pred["depth"]["final_depth"], self.K, self.image_size, s, cut, o["max_depth"],
+                                       out_from_cam=self.out_from_cam, min_range=o["min_range"], max_range=o["max_range"], stride=o["stride"],
+                                       image=self.image if o["rgb"] else None, with_pixel=bool(o["pixel"]), workspace=self.cloud_ws,
+                                       out=self.cloud_out)
+        if self.visualizer is not None:
+            out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
+        return out
+
+    def _load(self, buf, value, what, rows=False):
+        """value into the static buffer buf; rows: value may hold fewer leading rows than buf, the rest is left as it is."""
+        if not torch.is_tensor(value):
+            raise L.CrdError(f"LivePipeline.run: {what} must be a tensor")
+        dst = buf
+        if rows:
+            if value.dim() != buf.dim() or value.shape[0] > buf.shape[0]:
+                raise L.CrdError(f"LivePipeline.run: {what} {list(value.shape)} does not fit the capacity {list(buf.shape)}")
+            dst = buf[:value.shape[0]]
+        if value.dtype != buf.dtype or tuple(value.shape) != tuple(dst.shape):
+            raise L.CrdError(f"LivePipeline.run: {what} must be {buf.dtype} {list(dst.shape)}, not {value.dtype} {list(value.shape)}")
+        dst.copy_(value)
+
+    def run(self, frames, points=None, sweep_index=None, frame_offsets=None, cam1_from_sensor=None, cam2_from_sensor=None, lags=None, K=None,
+            out_from_cam=None, clone=False):
+        """One batch of sensor data through the graph.
+
+        frames: uint8 [B,H,W,frame_channels] with any strides (a view of a capture buffer; a host tensor is copied up).  points
+        [n,5], sweep_index [n], frame_offsets [B+1], cam1_from_sensor / cam2_from_sensor [S,3,4], lags [S,2]: radar_inputs' arguments
+        with n <= max_points and S <= max_sweeps, frame_offsets ending at or below n; a 3-channel model takes none of them.  K: fp64
+        [3,3] or [B,3,3], the camera's intrinsics at full resolution (the radar projection and the cloud read it; an RGB-only pipeline
+        without a cloud needs none).  out_from_cam: fp64 [3,4] or [B,3,4], the cloud's frame; None: the camera's own.
+
+        Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
+        output dictionary), 'cloud' and 'pictures' (if asked for at construction: the dictionaries of point_cloud and of
+        Visualizer.render).  They are VIEWS of this object's static buffers, valid until the next run(), which overwrites them in
+        place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call does not wait for the device."""
+        self._load(self.frames, frames, "frames")
+        radar_args = (points, sweep_index, frame_offsets, cam1_from_sensor, cam2_from_sensor, lags)
+        if self.radar_on:
+            if not all(torch.is_tensor(v) for v in radar_args) or K is None:
+                raise L.CrdError(f"LivePipeline.run: a model with radar channels takes the tensors {', '.join(RADAR_ARGS)} and K")
+            if points.shape[0] != sweep_index.shape[0] or not (cam1_from_sensor.shape[0] == cam2_from_sensor.shape[0] == lags.shape[0]):
+                raise L.CrdError(f"LivePipeline.run: {points.shape[0]} points with {sweep_index.shape[0]} sweep indices; sweep tables of "
+                                 f"{cam1_from_sensor.shape[0]}, {cam2_from_sensor.shape[0]} and {lags.shape[0]} rows")
+            for name, value in zip(RADAR_ARGS, radar_args):
+                self._load(getattr(self, name), value, name, rows=name != "frame_offsets")
+        elif any(v is not None for v in radar_args):
+            raise L.CrdError("LivePipeline.run: an RGB-only model takes no radar arguments")
+        if K is not None:
+            self._load(self.K, K.expand(self.B, 3, 3) if torch.is_tensor(K) and tuple(K.shape) == (3, 3) else K, "K")
+        elif self.cloud_opts is not None:
+            raise L.CrdError("LivePipeline.run: the point cloud needs K")
+        if out_from_cam is None:
+            self.out_from_cam.copy_(self.camera_frame)
+        else:
+            self._load(self.out_from_cam, out_from_cam.expand(self.B, 3, 4) if torch.is_tensor(out_from_cam) and
+                       tuple(out_from_cam.shape) == (3, 4) else out_from_cam, "out_from_cam")
+        self.plan.ensure_packed()                   # optimizer step / load_state_dict / mark_params_changed() since the last frame
+        self.graph.replay()
+        return _copies(self._results) if clone else dict(self._results)

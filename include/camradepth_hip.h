@@ -872,6 +872,39 @@ int crd_viz_draw(const void* src, int32_t kind, int32_t B, int32_t h, int32_t w,
 int crd_seg_labels(const float* logits, int32_t B, int32_t C, int32_t h, int32_t w, uint8_t* labels, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Camera front end: raw camera frames -> the network's image ("Camera front end").  The reference makes its `_im`
+ * image offline (scripts/prepare_flow_im.py:18-26, downsample_im): skimage.transform.resize(im, (H / 2, W / 2, 3), order=1,
+ * preserve_range=True, anti_aliasing=False).astype('uint8')[y_cutoff:] on the host in fp64.  One launch, no allocation, no
+ * synchronisation, capturable in a graph on one stream, arguments checked before any GPU call.  The entry adds no struct and changes
+ * no signature: CRD_ABI_VERSION stays.  tests/camera_ref.py restates the arithmetic in NumPy; the kernel agrees with it bit for bit.
+ *
+ * frames: uint8, B frames of im_h x im_w pixels of `channels` (3 or 4) bytes; pixel (y, x) of frame b begins at
+ * frames + b * frame_pitch + y * row_pitch + x * channels (pitches in bytes: a strided capture buffer needs no copy) and a fourth
+ * byte (alpha, padding) is ignored.  swap_rb != 0: stored channel k reads source byte 2 - k (frames in R, G, B as skimage.io.imread
+ * gives them, the network trained on cv2.imread's B, G, R); else byte k.
+ * Geometry, as for the other ends, s = downsample_scale: h_new = im_h / s, w_new = im_w / s, h = h_new - y_cutoff, w = w_new.
+ * Output pixel (r, c), stored channel k, with R = r + y_cutoff and p[y][x] the source byte of that channel:
+ *   s even, o = s / 2 - 1:  v = (p[R*s+o][c*s+o] + p[R*s+o][c*s+o+1] + p[R*s+o+1][c*s+o] + p[R*s+o+1][c*s+o+1]) >> 2
+ *   s odd:                  v = p[R*s + s/2][c*s + s/2]
+ * This is scikit-image 0.19.3's resize(order=1, anti_aliasing=False) -> scipy.ndimage.zoom(order=1, grid_mode=True) where s divides
+ * the frame: the sample point (R + 0.5) * s - 0.5 then lies midway between the two central pixels (even s: four weights of 1/4, the
+ * sum exact in fp64) or on a pixel (odd s), and astype('uint8') truncates.  s outside 1 .. 4 is refused.
+ * Outputs (either may be NULL, not both):
+ *   image_u8  uint8 [B][h][w][3], the layout of crd_assemble_input, of crd_point_cloud's image and of crd_viz_draw's
+ *   x         fp32 [B][x_channels][h][w], channels 0 .. 2 only: (v / 255 - mean[k]) / std[k], crd_assemble_input's own expression and
+ *             constants, indexed by the stored channel k -- the bits of crd_assemble_input on image_u8; channels >= 3 are not touched
+ * With s = 2, 3 channels and frames, row_pitch and frame_pitch multiples of 16, a thread makes eight adjacent pixels from three
+ * 16-byte loads of each of the two source rows; everything else, and the tail of a row, goes pixel by pixel.  Same bytes either way.
+ * CRD_E_INVALID: NULL frames; both outputs NULL; B, im_h or im_w <= 0; channels not 3 or 4; row_pitch < im_w * channels; frame_pitch <
+ * im_h * row_pitch; downsample_scale outside 1 .. 4; y_cutoff outside 0 .. h_new - 1; x with x_channels < 3; x not 4-byte aligned.
+ * CRD_E_UNSUPPORTED: im_h % s or im_w % s non-zero (the zoom factor is then not 1 / s and the rule above is not skimage's); B * h * w *
+ * max(3, x_channels) beyond the 32-bit indices.
+ * ------------------------------------------------------------------------------------------- */
+int crd_camera_frontend(const uint8_t* frames, int32_t B, int32_t im_h, int32_t im_w, int32_t channels, int64_t row_pitch,
+                        int64_t frame_pitch, int32_t swap_rb, int32_t downsample_scale, int32_t y_cutoff, uint8_t* image_u8, float* x,
+                        int32_t x_channels, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Losses (src/utils/loss_funcs.py:14-46,77-91; combination src/main/runner.py:197-218).
  * ------------------------------------------------------------------------------------------- */
 /* acc[0] += sum smooth_l1(pred-target), acc[1] += #(target>0), acc[2] += sum (target-pred)^2 ; crd_sum_t with
