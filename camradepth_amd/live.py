@@ -1,5 +1,6 @@
 """Raw sensors to depth, point cloud and pictures in ONE captured graph: the camera front end, the radar front end, the input
-assembly, the eval-mode network, the point-cloud back end and the visualiser on static buffers, replayed once per frame.
+assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid behind it, if asked for) and the visualiser
+on static buffers, replayed once per frame.
 
 Each stage exists on its own (camera.camera_inputs, radar.radar_inputs, batch.assemble_batch, inference.InferenceGraph,
 cloud.point_cloud, viz.Visualizer) and LivePipeline.run returns the bits of calling them one by one; what it adds is the ownership of
@@ -10,6 +11,7 @@ import math
 import torch
 
 from . import lib as L
+from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
 from .cloud import CloudWorkspace, point_cloud
 from .radar import RadarWorkspace, radar_inputs
@@ -17,6 +19,7 @@ from ._frontend import _size, map_shape
 from .viz import Visualizer
 
 CLOUD_OPTIONS = {"stride": 1, "min_range": 0.0, "max_range": math.inf, "max_depth": 100.0, "rgb": False, "pixel": False}
+BEV_OPTIONS = dict(GRID_OPTIONS, picture=False, picture_z_range=(-2.0, 4.0), cmap="jet")
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -40,15 +43,23 @@ class LivePipeline:
     pixel (3 or 4) and channel order; order_out: the order the network was trained on ('bgr', as cv2 reads).  max_depth, min_distance,
     min_z: as for assemble_batch and radar_inputs.
     cloud: None, or a dictionary of point_cloud's stride, min_range, max_range, max_depth, rgb (colours from the image) and pixel.
+    bev: None, or a dictionary of bev_grid's x_range, y_range, cell, z_range, min_points and flip, and picture (True: also the height
+    map in colours, bev.picture over picture_z_range in cmap).  It needs cloud=: the grid is laid in the cloud's frame, out_from_cam.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, Visualizer.render."""
+    point_cloud, bev_grid [, bev.picture], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
-                 frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None):
+                 frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
+                 bev=None):
         fn = "LivePipeline"
+        if bev is not None:
+            if cloud is None:
+                raise L.CrdError(f"{fn}: bev= needs cloud= (the grid is made from the point cloud, in its frame)")
+            if not isinstance(bev, dict) or not set(bev) <= set(BEV_OPTIONS):
+                raise L.CrdError(f"{fn}: bev= holds {sorted(BEV_OPTIONS)}, not {bev!r}")
         if model.flat is None or not model.flat.is_cuda:
             raise L.CrdError(f"{fn} needs the model on an MI355X (no CPU fallback)")
         Cin = model.cfg.input_channels
@@ -95,6 +106,13 @@ class LivePipeline:
         if self.cloud_opts is not None:
             self.cloud_ws = CloudWorkspace(B, self.image_size, self.downsample_scale, self.y_cutoff, self.cloud_opts["stride"], device=dev)
             self.cloud_out = self.cloud_ws.outputs(rgb=bool(self.cloud_opts["rgb"]), pixel=bool(self.cloud_opts["pixel"]))
+        self.bev_opts = None if bev is None else dict(BEV_OPTIONS, **bev)
+        if self.bev_opts is not None:
+            o = self.bev_opts
+            nx, ny = grid_shape(o["x_range"], o["y_range"], o["cell"])
+            self.bev_ws = BevWorkspace(B, nx, ny, device=dev)
+            self.bev_out = self.bev_ws.outputs()
+            self.bev_picture = torch.empty(B, nx, ny, 3, dtype=torch.uint8, device=dev) if o["picture"] else None
         self.visualizer = None if viz is None else Visualizer(B, h, w, **dict({"image_order": order_out, "device": dev}, **viz))
         # the eval plan, exactly as InferenceGraph takes it
         was_training = model.training
@@ -147,6 +165,13 @@ class LivePipeline:
                                        out_from_cam=self.out_from_cam, min_range=o["min_range"], max_range=o["max_range"], stride=o["stride"],
                                        image=self.image if o["rgb"] else None, with_pixel=bool(o["pixel"]), workspace=self.cloud_ws,
                                        out=self.cloud_out)
+            if self.bev_opts is not None:
+                o = self.bev_opts
+                grid = bev_grid(out["cloud"], x_range=o["x_range"], y_range=o["y_range"], cell=o["cell"], z_range=o["z_range"],
+                                min_points=o["min_points"], flip=o["flip"], workspace=self.bev_ws, out=self.bev_out)
+                out["bev"] = dict(grid)
+                if self.bev_picture is not None:
+                    out["bev"]["picture"] = picture(grid, o["picture_z_range"], o["cmap"], out=self.bev_picture)
         if self.visualizer is not None:
             out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
         return out
@@ -175,9 +200,10 @@ class LivePipeline:
         without a cloud needs none).  out_from_cam: fp64 [3,4] or [B,3,4], the cloud's frame; None: the camera's own.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud' and 'pictures' (if asked for at construction: the dictionaries of point_cloud and of
-        Visualizer.render).  They are VIEWS of this object's static buffers, valid until the next run(), which overwrites them in
-        place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call does not wait for the device."""
+        output dictionary), 'cloud', 'bev' and 'pictures' (if asked for at construction: the dictionaries of point_cloud, of bev_grid
+        -- with 'picture' if asked for -- and of Visualizer.render).  They are VIEWS of this object's static buffers, valid until the
+        next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call
+        does not wait for the device."""
         self._load(self.frames, frames, "frames")
         radar_args = (points, sweep_index, frame_offsets, cam1_from_sensor, cam2_from_sensor, lags)
         if self.radar_on:

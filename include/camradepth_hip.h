@@ -810,6 +810,62 @@ int crd_point_cloud(const float* depth, int32_t B, int32_t im_h, int32_t im_w, i
                     int32_t* frame_offsets, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bird's-eye-view back end: a point cloud -> per-cell grids in the caller's frame ("Bird's-eye-view back end").  The
+ * step after the point cloud, with its conventions: fp64 arithmetic, fp64 quantities through device memory or as IEEE-754 bit patterns
+ * (uint64_t ..._f64_bits), no allocation, no synchronisation, capturable in a graph on one stream, arguments checked before any GPU
+ * call.  The entry adds no struct and changes no signature: CRD_ABI_VERSION stays.  tests/bev_ref.py restates the arithmetic in NumPy;
+ * the kernels agree with it bit for bit.
+ *
+ * Rows.  xyz: fp32 [n_rows][3].  valid: uint8 [n_rows] or NULL (every row).  label: uint8 [n_rows] or NULL.  The frame of row p:
+ *   frame_offsets != NULL (int32 [B + 1] on the device, non-decreasing, read by the kernels; rows_per_frame must be 0): the b with
+ *     frame_offsets[b] <= p < frame_offsets[b + 1]; an empty frame repeats a value; a row outside every frame is ignored.  This is
+ *     crd_point_cloud's xyz with the frame_offsets it wrote.
+ *   frame_offsets == NULL (rows_per_frame > 0): b = p / rows_per_frame; rows with b >= B are ignored.  This is crd_depth_unproject's
+ *     points with its valid and rows_per_frame = h * w.
+ * grid_from_points: fp64 [3][4] row-major, one for all frames (t_stride 0) or one per frame (t_stride 12), or NULL: the identity.
+ *
+ * Row p of frame b, every operation rounded on its own (nothing is contracted into a fused multiply-add), (x, y, z) its three floats
+ * converted to fp64:
+ *   1. the row is skipped when valid != NULL and valid[p] == 0, or when it has no frame
+ *   2. X = T[0][0] * x + T[0][1] * y + T[0][2] * z + T[0][3], summed left to right; Y from row 1, Z from row 2;  NULL: (X, Y, Z) = (x, y, z)
+ *   3. skipped unless X, Y and Z are finite
+ *   4. Z = Z + 0.0                                  -0.0 becomes +0.0
+ *   5. skipped unless z_lo <= Z <= z_hi             +-inf bounds are allowed
+ *   6. qx = floor((X - x_min) / cell),  qy = floor((Y - y_min) / cell)
+ *   7. skipped unless 0 <= qx < nx and 0 <= qy < ny, compared as doubles: a point on a lower cell edge belongs to that cell, a point at
+ *      x_min + nx * cell is outside
+ *   8. its cell is [b][flip_x ? nx - 1 - qx : qx][flip_y ? ny - 1 - qy : qy]
+ * Outputs, each [B][nx][ny] and written in full; count and z_max are required, the others may be NULL:
+ *   count      int32   the rows of the cell                                                       empty cell: 0
+ *   z_max      fp32    the largest Z of the cell, rounded to fp32 once                            empty cell: the bit pattern 0x7fc00000
+ *   z_min      fp32    the smallest Z, rounded to fp32 once                                       empty cell: 0x7fc00000
+ *   top_index  int32   the row with the largest Z; among rows of equal fp64 Z the lowest index    empty cell: -1
+ *   top_label  uint8   label[top_index] (needs label)                                             empty cell: 255
+ *   occupancy  uint8   count >= min_points (min_points >= 1)                                      empty cell: 0
+ * 0x7fc00000 is a NaN: crd_viz_draw paints it in bad_rgb.
+ *
+ * The same bits every run: only integer minimum, maximum and add, whose results do not depend on the order of arrival.  The key of a
+ * height is its bit pattern with the sign bit flipped (Z >= 0) or with all bits flipped (Z < 0), which orders as the heights do.
+ * Launches on `stream`, no workgroup waiting on another: (0) clear the workspace and count; (1) per row an unsigned 64-bit atomic
+ * maximum and minimum of the key and an atomic add to count, the key atomics skipped where a plain read already settles them --
+ * neighbouring rows of one wave that share a cell are folded first and issue one set of atomics, which changes no result; (2) per
+ * row whose key is its cell's maximum an atomic minimum of the row index (only with top_index or top_label); (3) per cell the outputs.
+ * With n_rows == 0 launches (1) and (2) are left out and every cell is empty.
+ * workspace, 16-byte aligned, with n_cells = B * nx * ny: n_cells maximum keys (uint64); from the next multiple of 16 bytes n_cells
+ * minimum keys (uint64); from the next multiple of 16 bytes n_cells winners (uint32):
+ *   workspace_bytes >= 2 * ((8 * n_cells + 15) & ~15) + ((4 * n_cells + 15) & ~15).
+ * CRD_E_INVALID, nothing launched: NULL workspace, count or z_max, NULL xyz with n_rows > 0; xyz, frame_offsets or a 4-byte output not
+ * 4-byte aligned, grid_from_points not 8-byte, the workspace not 16-byte aligned; B <= 0; n_rows < 0; nx or ny outside 1 .. 65535;
+ * B * nx * ny >= 2^31; cell not finite and positive; x_min or y_min not finite; a NaN z bound or z_lo > z_hi; t_stride not 0 or 12;
+ * both or neither of frame_offsets and rows_per_frame; top_label without label; min_points < 1; a workspace too small.
+ * ------------------------------------------------------------------------------------------- */
+int crd_bev_grid(const float* xyz, const uint8_t* valid, const uint8_t* label, const int32_t* frame_offsets, int32_t rows_per_frame,
+                 int32_t B, int32_t n_rows, const double* grid_from_points, int32_t t_stride, uint64_t x_min_f64_bits,
+                 uint64_t y_min_f64_bits, uint64_t cell_f64_bits, int32_t nx, int32_t ny, uint64_t z_lo_f64_bits, uint64_t z_hi_f64_bits,
+                 int32_t min_points, int32_t flip_x, int32_t flip_y, void* workspace, int64_t workspace_bytes, int32_t* count, float* z_max,
+                 float* z_min, int32_t* top_index, uint8_t* top_label, uint8_t* occupancy, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
