@@ -1,5 +1,9 @@
 // Encoder-side kernels for gfx950: depthwise 3x3 (+wgrad) and the max-pool attention of the
 // Simplified Transformer (fused QK^T + scale + row-max on MFMA, rank-1 output, backward).
+// The head of the attention backward exists in two forms: k_attn_out_bwd + k_attn_scores_bwd + k_sum_partials_bf16 (three launches,
+// dS through memory, the rank-one vector path riding in the second; also the fallback for shapes whose masks do not fit in LDS), and
+// k_attn_bwd_fused + k_attn_dk_fold (two launches: output and score backward as one workgroup-local pass per pixel chunk, dS through
+// LDS, the vector path riding in the fold).  dx1, dS, dq and the dK partials are the same bits in both.
 #include <stdlib.h>
 #include "common.h"
 
@@ -662,10 +666,11 @@ __global__ __launch_bounds__(TPB) void k_attn_xbar_proj(XbarProj x) { attn_xbar_
 // Backward: tb = bf16(t); es[b][ci] = inv_n * sum_co W[co][ci] * tb[b][co], with wt the proj weight in its packed bf16
 // data-gradient form [C][Cpad] (row ci, contiguous over co).
 struct VecBwd { const crd_sum_t* t; const bf16_t* wt; int C, Cpad; float inv_n; bf16_t* tb; float* es; };
-__device__ __forceinline__ void attn_vec_bwd_body(const VecBwd& v, int b, int e) {
+// (part e owns `rows` rows of es; a row's sum does not depend on the split)
+__device__ __forceinline__ void attn_vec_bwd_body(const VecBwd& v, int b, int e, int rows = VEC_ROWS) {
   __shared__ float st[1024];
   const int C = v.C;
-  const int r_lo = e * VEC_ROWS, r_hi = r_lo + VEC_ROWS < C ? r_lo + VEC_ROWS : C;
+  const int r_lo = e * rows, r_hi = r_lo + rows < C ? r_lo + rows : C;
   float* eb = v.es + (long long)b * C;
   const float inv_n = v.inv_n;
   matvec_rows(v.wt, v.Cpad, r_lo, r_hi, C, st,
@@ -924,9 +929,221 @@ __global__ __launch_bounds__(TPB) void k_attn_scores_bwd(const bf16_t* q, const 
   }
 }
 
+// k_attn_out_bwd<PRE> and the LDS path of k_attn_scores_bwd as ONE workgroup-local pass over the scores kernel's pixel chunks (grid
+// (parts, B), parts = crd_attn_scores_bwd_partials): the score backward needs from the output backward only dS of its own pixels, a dot
+// product over one pixel's channels, so g = scale * dS goes from phase 1 to phase 2 through LDS instead of a launch boundary and a
+// round trip through memory.  The only grid-wide dependency of the pair, the rank-one vector path's need for the complete t, rides
+// in the launch that folds the dK partials instead (k_attn_dk_fold).  No workgroup waits for another.
+//   Phase 1 is k_attn_out_bwd's body on [p0, p1): the same lanes per pixel, per-element arithmetic and shuffle order, so dx1 and dS
+// are the same bits; t and dbp_rows are summed over other chunks than there (fixed-point adds: still reproducible).  Loads are
+// unconditional from clamped addresses, zeroed by selects.
+//   Phase 2 is k_attn_scores_bwd's: dq from gathered k rows, q rows and mask bits into LDS, the owner-computes dK walk, plain stores
+// of this chunk's partial copy.  The index and row loads of its first pass (the only one at chunks of <= 1024 granules) are
+// requested BEFORE phase 1: they depend on nothing phase 1 computes, and the launch is two memory latencies deep instead of four.
+struct ScoreBwd { const bf16_t* q; const bf16_t* k; const short* idx; int M, heads, d; float scale; bf16_t* dq; float* dk_part; };
+template <int UB>
+__device__ __forceinline__ void fused_load_index(const ScoreBwd& sb, int b, long long N, long long p0, int total, int i0,
+                                                 int (&cgv)[UB], int (&mv)[UB], long long (&nv)[UB]) {
+  const int CG = (sb.heads * sb.d) >> 3;
+#pragma unroll
+  for (int v = 0; v < UB; ++v) {
+    const int i = i0 + v * TPB;                     // (int: a chunk has at most 32767 pixels of 64 granules)
+    const int ic = i < total ? i : 0;               // (past the end: item 0, loaded and not used; no branch around the divisions)
+    cgv[v] = ic % CG;
+    nv[v] = p0 + ic / CG;
+    mv[v] = sb.idx[((long long)b * N + nv[v]) * sb.heads + (cgv[v] * 8) / sb.d];
+  }
+}
+template <int UB>
+__device__ __forceinline__ void fused_load_rows(const ScoreBwd& sb, int b, long long N, const int (&cgv)[UB], const int (&mv)[UB],
+                                                const long long (&nv)[UB], uint4 (&kraw)[UB], uint4 (&qraw)[UB]) {
+  const int C = sb.heads * sb.d;
+#pragma unroll
+  for (int v = 0; v < UB; ++v) {
+    kraw[v] = *reinterpret_cast<const uint4*>(sb.k + ((long long)b * sb.M + mv[v]) * C + cgv[v] * 8);
+    qraw[v] = *reinterpret_cast<const uint4*>(sb.q + ((long long)b * N + nv[v]) * C + cgv[v] * 8);
+  }
+}
+// dq = g * the gathered k rows; the q rows and one mask bit per (pixel, head) into LDS (k_attn_scores_bwd's pass with g from LDS)
+template <int UB>
+__device__ __forceinline__ void fused_scatter(const ScoreBwd& sb, int b, long long N, long long p0, int total, int i0,
+                                              const int (&cgv)[UB], const int (&mv)[UB], const long long (&nv)[UB], const uint4 (&kraw)[UB],
+                                              const uint4 (&qraw)[UB], uint4* sq, const float* sg, unsigned* mask, int WPC) {
+  const int C = sb.heads * sb.d, CG = C >> 3;
+#pragma unroll
+  for (int v = 0; v < UB; ++v) {
+    if (i0 + v * TPB >= total) continue;
+    const int nl = (int)(nv[v] - p0);
+    const float gv = sg[nl];
+    float kv[8];
+    kv[0] = bf_lo(kraw[v].x); kv[1] = bf_hi(kraw[v].x); kv[2] = bf_lo(kraw[v].y); kv[3] = bf_hi(kraw[v].y);
+    kv[4] = bf_lo(kraw[v].z); kv[5] = bf_hi(kraw[v].z); kv[6] = bf_lo(kraw[v].w); kv[7] = bf_hi(kraw[v].w);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) kv[j] *= gv;
+    store8_bf16(sb.dq, ((long long)b * N + nv[v]) * C + cgv[v] * 8, kv);
+    sq[nl * CG + cgv[v]] = make_uint4(qraw[v].x, qraw[v].y, qraw[v].z, qraw[v].w);      // (by element: the struct copy kept qraw in scratch)
+    const int h = (cgv[v] * 8) / sb.d;
+    // one bit per (pixel, head): integer LDS atomic, the result does not depend on the order
+    if (cgv[v] * 8 == h * sb.d) atomicOr(&mask[(h * sb.M + mv[v]) * WPC + (nl >> 5)], 1u << (nl & 31));
+  }
+}
+template <bool PRE>
+__global__ __launch_bounds__(TPB) void k_attn_bwd_fused(float* dx1, const float* u, const float* S, const float* dp, long long N, int chunk,
+                                                        crd_sum_t* t, crd_sum_t* dbp_rows, float* dS, GnPre pre, ScoreBwd sb) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.y;
+  const int M = sb.M, heads = sb.heads, d = sb.d;
+  const int C = heads * d, CG = C >> 3;
+  long long p0 = (long long)blockIdx.x * chunk, p1 = p0 + chunk;
+  if (p1 > N) p1 = N;
+  const int npx = (int)(p1 - p0);
+  const int HM = heads * M, WPC = (chunk + 31) >> 5;                           // mask words per (head, key)
+  uint4* sq = reinterpret_cast<uint4*>(smem);                                  // [chunk][CG]
+  float* sg = reinterpret_cast<float*>(smem + (size_t)chunk * C * 2);          // [chunk]: g = scale * dS
+  unsigned* mask = reinterpret_cast<unsigned*>(sg + chunk);                    // [HM][WPC]
+  float* sm = reinterpret_cast<float*>(mask + HM * WPC);                       // [2][C]: the waves' t / dbp sums
+  for (int i = threadIdx.x; i < HM * WPC; i += TPB) mask[i] = 0u;              // (published by the barriers of the wave fold below)
+  // ---- phase 2, loads: UB items per thread and pass, the index scalars of all of them, then the dependent row gathers
+  const int total = npx * CG;
+  constexpr int UB = 4;
+  int cgv[UB], mv[UB];
+  long long nv[UB];
+  uint4 kraw[UB], qraw[UB];
+  fused_load_index<UB>(sb, b, N, p0, total, threadIdx.x, cgv, mv, nv);
+  // ---- phase 1: k_attn_out_bwd on the chunk
+  int W2 = 1;
+  while (W2 < CG) W2 <<= 1;           // lanes per pixel (power of two, <= 64 since C <= 512)
+  const int PPW = 64 / W2;            // pixels per wave-iteration
+  const int l = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = l / W2, cg = l % W2;
+  const bool cok = cg < CG;
+  const int cgc = cok ? cg : 0;
+  const float dps = dp ? dp[b] : 1.f;
+  float uu[8], ta[8], ba[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { uu[j] = u[(long long)b * C + cgc * 8 + j]; uu[j] = cok ? uu[j] : 0.f; ta[j] = ba[j] = 0.f; }
+  float ga[8], mean = 0.f, rstd = 0.f, S1 = 0.f, S2 = 0.f;
+  if (PRE) {
+    if (b == 0 && pre.dgamma) {       // parameter gradients: the workgroups of sample 0 share the channels (as k_gn_bwd_apply)
+      for (int c = blockIdx.x * TPB + threadIdx.x; c < C; c += gridDim.x * TPB) {
+        const float ob = pre.dbeta[c], og = pre.dgamma[c];
+        long long g0, g1;
+        sum_samples(pre.r, pre.B, C, c, g0, g1);
+        pre.dbeta[c] = ob + (float)g0 * (1.f / GRAD_ONE);
+        pre.dgamma[c] = og + (float)g1 * (1.f / GRAD_ONE);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { ga[j] = pre.gamma[cgc * 8 + j]; ga[j] = cok ? ga[j] : 0.f; }
+    if (cok) {
+      const int grp = cg >> 1;                                    // 16-channel groups (gmul = 1)
+      const float inv_m = 1.f / ((float)N * 16.f);
+      const crd_sum_t* rg = pre.r + (long long)pre.B * C * 2 + ((long long)b * (C >> 4) + grp) * 2;
+      S1 = grad_get(rg) * inv_m; S2 = grad_get(rg + 1) * inv_m;
+      gn_mean_rstd(pre.stats + (long long)b * (C >> 4) * 2, grp, 1, (float)N * 16.f, mean, rstd);
+    }
+  }
+  fused_load_rows<UB>(sb, b, N, cgv, mv, nv, kraw, qraw);
+  constexpr int UN = 4;
+  for (long long nb = p0 + wave * PPW; nb < p1; nb += (long long)UN * 4 * PPW) {
+    float v[UN][8], s[UN];
+    float xv[PRE ? UN : 1][8], dv[PRE ? UN : 1][8];
+#pragma unroll
+    for (int k = 0; k < UN; ++k) {
+      const long long n = nb + (long long)k * 4 * PPW + sub;
+      const bool ok = cok && n < p1;
+      const long long nc = n < p1 ? n : p1 - 1;
+      const long long off = ((long long)b * N + nc) * C + cgc * 8;
+      load8(dx1, off, 1, v[k]);
+      s[k] = S[(long long)b * N + nc];
+      if (PRE) { load8(pre.x, off, 1, xv[PRE ? k : 0]); load8(pre.dxn, off, 0, dv[PRE ? k : 0]); }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[k][j] = ok ? v[k][j] : 0.f;
+      s[k] = ok ? s[k] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < UN; ++k) {
+      const long long n = nb + (long long)k * 4 * PPW + sub;
+      if (PRE && cok && n < p1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float xh = (xv[PRE ? k : 0][j] - mean) * rstd;
+          float o = (ga[j] * dv[PRE ? k : 0][j] - S1 - xh * S2) * rstd;
+          o += v[k][j];
+          v[k][j] = o;
+        }
+        store8_f32(dx1, ((long long)b * N + n) * C + cg * 8, v[k]);
+      }
+      float dot = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { v[k][j] *= dps; dot += v[k][j] * uu[j]; ta[j] += v[k][j] * s[k]; ba[j] += v[k][j]; }
+      for (int o = W2 >> 1; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+      if (cok && n < p1 && cg == 0) {
+        sg[n - p0] = sb.scale * dot;
+        if (dS) dS[(long long)b * N + n] = dot;
+      }
+    }
+  }
+  for (int o = W2; o < 64; o <<= 1) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { ta[j] += __shfl_xor(ta[j], o); ba[j] += __shfl_xor(ba[j], o); }
+  }
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w && sub == 0 && cok) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float* p0_ = &sm[cg * 8 + j];
+        float* p1_ = &sm[C + cg * 8 + j];
+        *p0_ = w == 0 ? ta[j] : *p0_ + ta[j];
+        *p1_ = w == 0 ? ba[j] : *p1_ + ba[j];
+      }
+    }
+    __syncthreads();                  // (the last one also publishes sg and the zeroed masks to phase 2)
+  }
+  for (int i = threadIdx.x; i < C; i += TPB) {
+    grad_add(&t[(long long)b * C + i], sm[i]);
+    grad_add(&dbp_rows[(long long)b * C + i], sm[C + i]);
+  }
+  // ---- phase 2: k_attn_scores_bwd's LDS path with g from LDS; the first pass consumes the rows requested at the top
+  fused_scatter<UB>(sb, b, N, p0, total, threadIdx.x, cgv, mv, nv, kraw, qraw, sq, sg, mask, WPC);
+  for (int i0 = threadIdx.x + UB * TPB; i0 < total; i0 += UB * TPB) {      // chunks of more than 1024 granules
+    int cg2[UB], m2[UB];
+    long long n2[UB];
+    uint4 k2[UB], q2[UB];
+    fused_load_index<UB>(sb, b, N, p0, total, i0, cg2, m2, n2);
+    fused_load_rows<UB>(sb, b, N, cg2, m2, n2, k2, q2);
+    fused_scatter<UB>(sb, b, N, p0, total, i0, cg2, m2, n2, k2, q2, sq, sg, mask, WPC);
+  }
+  __syncthreads();
+  // the owner of (key m, granule cg) walks the set bits of the key's mask in ascending pixel order (as k_attn_scores_bwd)
+  float* outp = sb.dk_part + ((long long)blockIdx.x * gridDim.y + b) * M * C;
+  for (int pr = threadIdx.x; pr < M * CG; pr += TPB) {
+    const int m = pr / CG, cgo = pr - m * CG;
+    const int h = (cgo * 8) / d;
+    const unsigned* mk = mask + (h * M + m) * WPC;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    for (int w = 0; w < WPC; ++w) {
+      unsigned bits = mk[w];
+      while (bits) {
+        const int n = (w << 5) + __builtin_ctz(bits);
+        bits &= bits - 1;
+        const uint4 q8 = sq[n * CG + cgo];
+        const float g = sg[n];
+        acc[0] += g * bf_lo(q8.x); acc[1] += g * bf_hi(q8.x); acc[2] += g * bf_lo(q8.y); acc[3] += g * bf_hi(q8.y);
+        acc[4] += g * bf_lo(q8.z); acc[5] += g * bf_hi(q8.z); acc[6] += g * bf_lo(q8.w); acc[7] += g * bf_hi(q8.w);
+      }
+    }
+    store8_f32(outp, (long long)m * C + cgo * 8, acc);
+  }
+}
+
 // dst[i] = bf16(sum_r part[r*stride + i]), 8 elements per thread
-__global__ __launch_bounds__(TPB) void k_sum_partials_bf16(const float* part, int replicas, long long stride, bf16_t* dst, long long n8) {
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n8; i += (long long)gridDim.x * TPB) {
+// (workgroup blk of nblk: k_attn_dk_fold runs the same fold behind its rider workgroups)
+__device__ __forceinline__ void sum_partials_body(const float* part, int replicas, long long stride, bf16_t* dst, long long n8, int blk,
+                                                  int nblk) {
+  for (long long i = (long long)blk * TPB + threadIdx.x; i < n8; i += (long long)nblk * TPB) {
     // the copies four at a time, all loads of a pass in flight (clamped index, select past the end; still added in index
     // order): one copy per iteration was one dependent memory latency per copy -- 52 of them at stage 1
     float v[8];
@@ -945,6 +1162,20 @@ __global__ __launch_bounds__(TPB) void k_sum_partials_bf16(const float* part, in
     }
     store8_bf16(dst, i * 8, v);
   }
+}
+__global__ __launch_bounds__(TPB) void k_sum_partials_bf16(const float* part, int replicas, long long stride, bf16_t* dst, long long n8) {
+  sum_partials_body(part, replicas, stride, dst, n8, blockIdx.x, gridDim.x);
+}
+// The fold of k_attn_bwd_fused's dK partials with the rank-one vector path as riders: the first B * cdiv(C, FOLD_VEC_ROWS) workgroups
+// run attn_vec_bwd_body (sample-major), the rest are k_sum_partials_bf16's.  t is complete when this launch starts (it sits behind the
+// launch that adds it up), and tb / es are first read behind it.  A rider owns 16 rows, one batch of four per wave, requested before t
+// is read: with VEC_ROWS rows (four dependent batches) the riders ended the launch 3 us behind the fold workgroups.
+constexpr int FOLD_VEC_ROWS = 16;
+__global__ __launch_bounds__(TPB) void k_attn_dk_fold(const float* part, int replicas, long long stride, bf16_t* dst, long long n8, int B,
+                                                      VecBwd vec) {
+  const int nv = (vec.C + FOLD_VEC_ROWS - 1) / FOLD_VEC_ROWS, nrider = B * nv;
+  if ((int)blockIdx.x < nrider) { attn_vec_bwd_body(vec, blockIdx.x / nv, blockIdx.x % nv, FOLD_VEC_ROWS); return; }
+  sum_partials_body(part, replicas, stride, dst, n8, blockIdx.x - nrider, gridDim.x - nrider);
 }
 
 // dst[i] = bf16(value of the fixed-point gradient sum src[i]), 8 elements per thread
@@ -1242,6 +1473,68 @@ extern "C" int crd_sum_partials_bf16(const float* part, int32_t replicas, int64_
   hipLaunchKernelGGL(k_sum_partials_bf16, dim3((unsigned)nb), dim3(TPB), 0, as_stream(stream), part, replicas, (long long)replica_stride,
                      reinterpret_cast<bf16_t*>(dst), (long long)(n / 8));
   CRD_LAUNCH_CHECK("crd_sum_partials_bf16");
+  return CRD_OK;
+}
+
+// LDS of k_attn_bwd_fused: the chunked score path's plus the [2][C] sums of the output backward
+static size_t attn_bwd_fused_lds(int chunk, int M, int heads, int C) { return attn_bwd_lds(chunk, M, heads, C) + 2 * (size_t)C * sizeof(float); }
+// workgroups per sample of k_attn_bwd_fused = the score backward's chunk rule; 0: this shape stays on the separate launches
+static int attn_bwd_fused_blocks(int B, int N, int M, int heads, int C) {
+  if (B < 1 || N < 1 || M < 1 || heads < 1 || C < 8 || C % 8 || C > 512) return 0;
+  const int nblk = attn_bwd_blocks(B, N, M, heads, C);
+  if (nblk == 0 || attn_bwd_fused_lds(cdiv(N, nblk), M, heads, C) > 128 * 1024) return 0;
+  return nblk;
+}
+
+extern "C" int crd_attn_bwd_fused_supported(int32_t B, int32_t N, int32_t M, int32_t heads, int32_t d) {
+  return d > 0 && d % 8 == 0 && heads > 0 ? attn_bwd_fused_blocks(B, N, M, heads, heads * d) : 0;
+}
+
+extern "C" int crd_attn_bwd_fused(float* dx1, const float* u, const float* S, const float* dp, const void* q, const void* k, const int16_t* idx,
+                                  int32_t B, int32_t N, int32_t M, int32_t heads, int32_t d, float scale, crd_sum_t* t, crd_sum_t* dbp_rows,
+                                  float* dS, void* dq, float* dk_partials, const float* x, const void* dxn, const crd_sum_t* stats,
+                                  const float* gamma, const crd_sum_t* r, float* dgamma, float* dbeta, crd_stream_t stream) {
+  CRD_CHECK_ARG(dx1 && u && S && q && k && idx && t && dbp_rows && dq && dk_partials, "crd_attn_bwd_fused: null pointer");
+  CRD_CHECK_ARG(B > 0 && N > 0 && M > 0 && heads > 0, "crd_attn_bwd_fused: B, N, M and heads must be positive");
+  CRD_CHECK_ARG(d > 0 && d % 8 == 0, "crd_attn_bwd_fused: head dim must be a multiple of 8");
+  const bool pre = x || dxn || stats || gamma || r || dgamma || dbeta;
+  const int C = heads * d;
+  CRD_UNSUPPORTED(C <= 512, "crd_attn_bwd_fused: C = %d must be <= 512", C);
+  if (pre) {
+    CRD_CHECK_ARG(x && dxn && stats && gamma && r, "crd_attn_bwd_fused: null pointer (GroupNorm backward)");
+    CRD_CHECK_ARG(C % 16 == 0 && (dgamma == nullptr) == (dbeta == nullptr), "crd_attn_bwd_fused: C %% 16, dgamma / dbeta both or neither");
+  }
+  const int nblk = attn_bwd_fused_blocks(B, N, M, heads, C);
+  CRD_UNSUPPORTED(nblk > 0, "crd_attn_bwd_fused: a pixel chunk (q rows, g, masks, 2 * C channel sums) does not fit in LDS "
+                            "(crd_attn_bwd_fused_supported = 0)");
+  const int chunk = cdiv(N, nblk);
+  const size_t lds = attn_bwd_fused_lds(chunk, M, heads, C);
+  const ScoreBwd sb{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const short*>(idx), M, heads, d,
+                    scale, reinterpret_cast<bf16_t*>(dq), dk_partials};
+  if (pre) {
+    crd_reserve_lds_once<&k_attn_bwd_fused<true>>(128 * 1024, "k_attn_bwd_fused<true>");
+    hipLaunchKernelGGL(k_attn_bwd_fused<true>, dim3(nblk, B), dim3(TPB), lds, as_stream(stream), dx1, u, S, dp, (long long)N, chunk, t,
+                       dbp_rows, dS, GnPre{x, reinterpret_cast<const bf16_t*>(dxn), stats, gamma, r, dgamma, dbeta, B}, sb);
+  } else {
+    crd_reserve_lds_once<&k_attn_bwd_fused<false>>(128 * 1024, "k_attn_bwd_fused<false>");
+    hipLaunchKernelGGL(k_attn_bwd_fused<false>, dim3(nblk, B), dim3(TPB), lds, as_stream(stream), dx1, u, S, dp, (long long)N, chunk, t,
+                       dbp_rows, dS, GnPre{}, sb);
+  }
+  CRD_LAUNCH_CHECK("crd_attn_bwd_fused");
+  return CRD_OK;
+}
+
+extern "C" int crd_attn_dk_fold(const float* part, int32_t replicas, int64_t replica_stride, void* dst, int64_t n, const crd_sum_t* t,
+                                const void* w_dgrad, int32_t B, int32_t C, int32_t Cpad, float inv_n, void* tb, float* es, crd_stream_t stream) {
+  CRD_CHECK_ARG(part && dst && replicas >= 1 && n > 0 && n % 8 == 0 && replica_stride % 8 == 0, "crd_attn_dk_fold: bad argument");
+  CRD_CHECK_ARG(t && w_dgrad && tb && es && B > 0, "crd_attn_dk_fold: null pointer");
+  CRD_UNSUPPORTED(C > 0 && C % 8 == 0 && C <= 1024 && Cpad >= C && Cpad % 8 == 0, "crd_attn_dk_fold: C must be a multiple of 8, <= 1024");
+  long long nb = (n / 8 + TPB - 1) / TPB;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(k_attn_dk_fold, dim3((unsigned)(nb + (long long)B * cdiv(C, FOLD_VEC_ROWS))), dim3(TPB), 0, as_stream(stream), part, replicas,
+                     (long long)replica_stride, reinterpret_cast<bf16_t*>(dst), (long long)(n / 8), B,
+                     VecBwd{t, reinterpret_cast<const bf16_t*>(w_dgrad), C, Cpad, inv_n, reinterpret_cast<bf16_t*>(tb), es});
+  CRD_LAUNCH_CHECK("crd_attn_dk_fold");
   return CRD_OK;
 }
 

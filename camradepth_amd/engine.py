@@ -22,6 +22,7 @@ import torch
 from . import lib as L
 from . import trace
 from . import plan_tables as tables
+from . import plan_values
 from .config import MID_CHANNELS, UNSUP_CLASSES
 from .plan_desc import make_desc
 from .plan_values import (BF16, F32, SUM, PM, ConvW, Op, _BufPtr, _Lazy, _WPtr, conv3p_tile, dgrad_flops, fp8_tile,  # noqa: F401
@@ -46,7 +47,7 @@ def _dev_int(name, default):
 #   Mlp.norm2's backward reduce in fc2's data-gradient epilogue on every grid: 26.6 vs 26.4 ms (18.01 vs 17.91 on the wide kernel) --
 #     kept only on grids of <= FUSE_GN_RED_MAXPIX pixels per sample, where the launch it saves wins (25.2 -> 25.0 ms);
 #   always on: grouped small weight gradients, GroupNorm statistics from the producing kernels, the ragged-tile split of 3x3 data
-#     gradients, per-split partial copies in the streaming 3x3 weight gradient, Block.norm2's backward apply inside crd_attn_out_bwd_gn,
+#     gradients, per-split partial copies in the streaming 3x3 weight gradient, Block.norm2's backward apply inside crd_attn_bwd_fused / crd_attn_out_bwd_gn,
 #     Block.norm1 / norm2 reduces in GEMM epilogues, write-once K-concatenated decoder data gradients.
 FUSE_GN_RED_MAXPIX = _dev_int("CRD_FUSE_GN_RED_MAXPIX", 416)
 
@@ -1069,7 +1070,11 @@ class Plan:
         vars(t).update(rb2=rb2, dh_out=dh_out)
 
     def _attn_bwd(self, t, g):
-        """d(x1) (DX + Block.norm2's backward apply of DXN) -> attention output -> scores -> q and the key path -> Block.norm1: DX = d(X)."""
+        """d(x1) (DX + Block.norm2's backward apply of DXN) -> attention output -> scores -> q and the key path -> Block.norm1: DX = d(X).
+        The head is two launches where the stage's bit of plan_values.ATTN_BWD_FUSED is set and the library covers the shape
+        (crd_attn_bwd_fused_supported): crd_attn_bwd_fused (norm2's apply, the output backward and the score backward of a pixel
+        chunk in one workgroup, scale * dS handed over in LDS) and crd_attn_dk_fold (the fold of the dK partials + the rank-one vector
+        path, which needs the complete T).  Otherwise three: crd_attn_out_bwd(_gn), crd_attn_bwd, crd_sum_partials_bf16 / crd_gsum_to_bf16."""
         B = self.B
         name, a, stage_i, X, DX, DXN, dp, dh_prev, rb2 = t.name, t.a, t.stage_i, t.X, t.DX, t.DXN, t.dp, t.dh_prev, t.rb2
         Cs, heads, sr, Hs, Ws, N, M, dh, scale = t.Cs, t.heads, t.sr, t.Hs, t.Ws, t.N, t.M, t.dh, t.scale
@@ -1077,34 +1082,54 @@ class Plan:
         if sr > 1:
             KR, stk, KRN, csr = t.kr, t.stk, t.krn, t.csr
         DQ = self.act(Cs, Hs, Ws)
-        Tv, dSv = self.zb(B, Cs), self.new((B, N), F32)
+        Tv = self.zb(B, Cs)
         dbp_rows = self.zb(B, Cs)
         self.row_grads.append((a + ".proj.bias", Cs, dbp_rows, B, self._tag, 0, Cs))
-        if rb2 is not None and Cs <= 512:
-            # the apply phase of Block.norm2's backward (DX += ...: DX = d(X1)) runs inside the launch that reads DX next
-            self._emit(g, "crd_attn_out_bwd_gn", [DX.t, U.t, Ssum, dp, B, N, Cs, Tv, dbp_rows, dSv, X1.t, DXN.t, st2,
-                                                   self.p(name + ".norm2.weight"), rb2, self.g(name + ".norm2.weight"),
-                                                   self.g(name + ".norm2.bias")], io=nbytes(DX, DX, X1, DXN, Ssum, dSv))
-        else:
-            self.gn_bwd(g, X1, st2, 1, name + ".norm2", 0, None, DXN, DX, dx_acc=1, r=rb2)       # DX = d(X1)
-            self._emit(g, "crd_attn_out_bwd", [DX.t, U.t, Ssum, dp, B, N, Cs, Tv, dbp_rows, dSv], io=nbytes(DX, Ssum, dSv))
         Tb = PM(self.new((B, 1, Cs)), Cs, 1, 1)
         Es = PM(self.new((B, 1, Cs), F32), Cs, 1, 1)
-        # rank-one vector path (Tb = bf16(T), Es = d(xbar)/N: the bias of the q data gradient) rides in the launch of the
-        # score backward: both consume attn_out_bwd's outputs.
+        # rank-one vector path (Tb = bf16(T), Es = d(xbar)/N: the bias of the q data gradient): extra workgroups of a launch behind
+        # the one that completes T
         vec = [Tv, _WPtr(cp, "w_dgrad"), cp.cout_pad, 1.0 / N, Tb.t, Es.t]
         # dK: per-workgroup partial accumulators (plain stores) folded by the bf16 conversion below; fp32-atomic
         # accumulation into one buffer only when [M][C] does not fit in LDS
         nparts = self.lib.crd_attn_scores_bwd_partials(B, N, M, heads, dh)
-        if nparts > 0:
+        fused = ((_dev_int("CRD_ATTN_BWD_FUSED", plan_values.ATTN_BWD_FUSED) >> stage_i) & 1
+                 and self.lib.crd_attn_bwd_fused_supported(B, N, M, heads, dh) > 0)         # (the entry's own rule: it never refuses here)
+        gn_pre = rb2 is not None and Cs <= 512
+        if not gn_pre:
+            self.gn_bwd(g, X1, st2, 1, name + ".norm2", 0, None, DXN, DX, dx_acc=1, r=rb2)       # DX = d(X1)
+        DKb = None
+        if fused:
+            # ONE workgroup-local pass: the output backward hands scale * dS of a pixel chunk to the score backward through LDS (no dS
+            # buffer, a dependent launch less per Block); the vector path rides in the fold of the dK partials, right behind it
             self.scratch("attn_parts", nparts * B * M * Cs)
-            dK = None
-            self._emit(g, "crd_attn_bwd", [Q.t, K.t, dSv, idx, B, N, M, heads, dh, scale, DQ.t, None, self.attn_parts] + vec,
-                       io=nbytes(Q, K, dSv, idx, DQ) + nparts * B * M * Cs * 4)
+            dK, DKb = None, self.act(Cs, Hs // sr, Ws // sr)
+            pre = [X1.t, DXN.t, st2, self.p(name + ".norm2.weight"), rb2, self.g(name + ".norm2.weight"),
+                   self.g(name + ".norm2.bias")] if gn_pre else [None] * 7
+            self._emit(g, "crd_attn_bwd_fused", [DX.t, U.t, Ssum, dp, Q.t, K.t, idx, B, N, M, heads, dh, scale, Tv, dbp_rows, None, DQ.t,
+                                                  self.attn_parts] + pre,
+                       io=(nbytes(DX, DX, X1, DXN, Ssum) if gn_pre else nbytes(DX, Ssum)) + nbytes(Q, K, idx, DQ) + nparts * B * M * Cs * 4)
+            self._emit(g, "crd_attn_dk_fold", [self.attn_parts, nparts, B * M * Cs, DKb.t, B * M * Cs, Tv, _WPtr(cp, "w_dgrad"), B, Cs,
+                                                cp.cout_pad, 1.0 / N, Tb.t, Es.t], io=nparts * B * M * Cs * 4 + nbytes(DKb))
         else:
-            dK = self.zb(B, M, Cs)
-            self._emit(g, "crd_attn_bwd", [Q.t, K.t, dSv, idx, B, N, M, heads, dh, scale, DQ.t, dK, None] + vec,
-                       io=nbytes(Q, K, dSv, idx, DQ, dK))
+            dSv = self.new((B, N), F32)
+            if gn_pre:
+                # the apply phase of Block.norm2's backward (DX += ...: DX = d(X1)) runs inside the launch that reads DX next
+                self._emit(g, "crd_attn_out_bwd_gn", [DX.t, U.t, Ssum, dp, B, N, Cs, Tv, dbp_rows, dSv, X1.t, DXN.t, st2,
+                                                       self.p(name + ".norm2.weight"), rb2, self.g(name + ".norm2.weight"),
+                                                       self.g(name + ".norm2.bias")], io=nbytes(DX, DX, X1, DXN, Ssum, dSv))
+            else:
+                self._emit(g, "crd_attn_out_bwd", [DX.t, U.t, Ssum, dp, B, N, Cs, Tv, dbp_rows, dSv], io=nbytes(DX, Ssum, dSv))
+            # the vector path rides in the launch of the score backward: both consume attn_out_bwd's outputs
+            if nparts > 0:
+                self.scratch("attn_parts", nparts * B * M * Cs)
+                dK = None
+                self._emit(g, "crd_attn_bwd", [Q.t, K.t, dSv, idx, B, N, M, heads, dh, scale, DQ.t, None, self.attn_parts] + vec,
+                           io=nbytes(Q, K, dSv, idx, DQ) + nparts * B * M * Cs * 4)
+            else:
+                dK = self.zb(B, M, Cs)
+                self._emit(g, "crd_attn_bwd", [Q.t, K.t, dSv, idx, B, N, M, heads, dh, scale, DQ.t, dK, None] + vec,
+                           io=nbytes(Q, K, dSv, idx, DQ, dK))
         self.wgrad(g, xbar, Tb, cp, 1, 1, 0, 1, 1)
         self.wgrad(g, XN, DQ, cq, 1, 1, 0, Hs, Ws, dbias=a + ".q.bias")
         # d(norm1(X)) = q's data gradient (+ the rank-one vector path's Es) + the key path's.  With the fused reduce the key path
@@ -1117,10 +1142,13 @@ class Plan:
         else:
             q_dgrad.update(accumulate=1, red=(X, st1, self.p(name + ".norm1.weight"), self.p(name + ".norm1.bias"), 1, 0, rb1))
         key_acc = 1 if rb1 is None else 0
-        DKb = self.act(Cs, Hs // sr, Ws // sr)
-        if dK is None:
+        if DKb is not None:
+            pass                                  # folded by crd_attn_dk_fold above
+        elif dK is None:
+            DKb = self.act(Cs, Hs // sr, Ws // sr)
             self._emit(g, "crd_sum_partials_bf16", [self.attn_parts, nparts, B * M * Cs, DKb.t, B * M * Cs], io=nparts * B * M * Cs * 4 + nbytes(DKb))
         else:
+            DKb = self.act(Cs, Hs // sr, Ws // sr)
             self._emit(g, "crd_gsum_to_bf16", [dK, DKb.t, B * M * Cs], io=nbytes(dK, DKb))
         if sr > 1:
             DKR = self.act(Cs, Hs // sr, Ws // sr)

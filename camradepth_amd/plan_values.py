@@ -12,6 +12,12 @@ BF16, F32 = torch.bfloat16, torch.float32
 SUM = torch.int64    # crd_sum_t: the 64-bit fixed-point accumulators every multi-workgroup "+=" goes through (include/camradepth_hip.h)
 
 
+# Encoder stages (bit s = stage s + 1) whose Blocks run the head of the attention backward as crd_attn_bwd_fused + crd_attn_dk_fold
+# instead of crd_attn_out_bwd(_gn) + crd_attn_bwd + crd_sum_partials_bf16 (engine.Plan._attn_bwd; DESIGN.md section 4 has the A/B).
+# CRD_ATTN_BWD_FUSED overrides it under CRD_DEV_SWITCHES=1, read when a plan is built.
+ATTN_BWD_FUSED = 15
+
+
 def rup(x, m=8):
     return (x + m - 1) // m * m
 

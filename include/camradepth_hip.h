@@ -463,6 +463,31 @@ int crd_attn_bwd(const void* q, const void* k, const float* dS, const int16_t* i
 /* dst[i] = bf16(sum_{r < replicas} part[r*replica_stride + i]), i < n (n, replica_stride multiples of 8) */
 int crd_sum_partials_bf16(const float* part, int32_t replicas, int64_t replica_stride, void* dst, int64_t n,
                           crd_stream_t stream);
+/* crd_attn_out_bwd (x == NULL) or crd_attn_out_bwd_gn (x != NULL: x, dxn, stats, gamma, r required, dgamma / dbeta both or neither,
+ * C % 16 == 0) and the partial form of crd_attn_scores_bwd in ONE launch, without the round trip of dS through memory: a workgroup
+ * runs the output backward on one of the score backward's pixel chunks, hands g = scale * dS to the score backward through LDS
+ * and goes on with it.  Grid (P, B), P = crd_attn_scores_bwd_partials(B, N, M, heads, d); C = heads * d.
+ *   dx1 (written with x != NULL only), dq and dk_partials (float [P][B][M][C], contents don't-care, every element stored) are bit
+ * for bit what the two calls give; dS (float [B][N]) is too and may be NULL: it is then not stored.  t and dbp_rows (crd_sum_t
+ * [B][C], zeroed by the caller) are fixed-point sums of per-workgroup float sums over P chunks instead of crd_attn_out_bwd_blocks
+ * ones: reproducible from run to run, and equal to the two calls' to fp32 rounding.  The rank-one vector path (crd_attn_vec_bwd)
+ * needs the complete t and is NOT part of this launch: crd_attn_dk_fold runs it.
+ *   CRD_E_UNSUPPORTED, and nothing launched, exactly where crd_attn_bwd_fused_supported returns 0: P == 0 (the masks of a chunk do
+ * not fit in LDS: the caller keeps the separate calls, whose fallback adds into a dk accumulator), C > 512 (crd_attn_out_bwd's
+ * limit), or a chunk's LDS (q rows, g, masks and the 2 * C channel sums) above 128 KB.  A new entry, no changed signature:
+ * CRD_ABI_VERSION stays. */
+/* Does crd_attn_bwd_fused take this shape?  Its workgroups per sample (= crd_attn_scores_bwd_partials) or 0; host arithmetic only, the
+ * rule the entry itself applies, so a caller that asks first is never refused for the shape. */
+int crd_attn_bwd_fused_supported(int32_t B, int32_t N, int32_t M, int32_t heads, int32_t d);
+int crd_attn_bwd_fused(float* dx1, const float* u, const float* S, const float* dp, const void* q, const void* k, const int16_t* idx,
+                       int32_t B, int32_t N, int32_t M, int32_t heads, int32_t d, float scale, crd_sum_t* t, crd_sum_t* dbp_rows,
+                       float* dS, void* dq, float* dk_partials, const float* x, const void* dxn, const crd_sum_t* stats,
+                       const float* gamma, const crd_sum_t* r, float* dgamma, float* dbeta, crd_stream_t stream);
+/* crd_sum_partials_bf16(part, replicas, replica_stride, dst, n) and crd_attn_vec_bwd(t, w_dgrad, B, C, Cpad, inv_n, tb, es) in
+ * ONE launch: B * ceil(C / 16) extra workgroups run the vector path.  The launch behind crd_attn_bwd_fused: t is complete when
+ * it starts, and nothing reads tb / es before it.  dst, tb and es are bit for bit the two calls'.  A new entry: CRD_ABI_VERSION stays. */
+int crd_attn_dk_fold(const float* part, int32_t replicas, int64_t replica_stride, void* dst, int64_t n, const crd_sum_t* t,
+                     const void* w_dgrad, int32_t B, int32_t C, int32_t Cpad, float inv_n, void* tb, float* es, crd_stream_t stream);
 /* dst[i] = bf16(src[i] * 2^-CRD_GRAD_FRAC_BITS), i < n (n a multiple of 8): the dk accumulator of crd_attn_scores_bwd's
  * global path as the bf16 operand the next layer needs */
 int crd_gsum_to_bf16(const crd_sum_t* src, void* dst, int64_t n, crd_stream_t stream);
