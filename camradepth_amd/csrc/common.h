@@ -148,6 +148,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// the 8 bf16 channels of a 16-byte granule as floats
+__device__ __forceinline__ void unpack8(const uint4& u, float (&v)[8]) {
+  v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
+  v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
+}
 // load 8 consecutive channels as floats from a bf16 or fp32 row
 __device__ __forceinline__ void load8(const void* base, int64_t elem_off, int is_f32, float (&v)[8]) {
   if (is_f32) {
@@ -155,9 +160,7 @@ __device__ __forceinline__ void load8(const void* base, int64_t elem_off, int is
     float4 a = p[0], b = p[1];
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
   } else {
-    uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + elem_off);
-    v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
-    v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
+    unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + elem_off), v);
   }
 }
 template <int F32>
@@ -167,9 +170,7 @@ __device__ __forceinline__ void load8t(const void* base, long long elem_off, flo
     float4 a = p[0], b = p[1];
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
   } else {
-    uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + elem_off);
-    v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
-    v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
+    unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + elem_off), v);
   }
 }
 __device__ __forceinline__ void store8_bf16(void* base, int64_t elem_off, const float (&v)[8]) {

@@ -123,7 +123,7 @@ def test_support_query_is_the_rule_of_the_plan_and_of_the_entry(built):
     B, N, M, heads, d = gap = (1, 550, 1000, 8, 64)
     parts = L.crd_attn_scores_bwd_partials(*gap)
     chunk, C_ = -(-N // parts), heads * d
-    need = chunk * C_ * 2 + chunk * 4 + heads * M * (-(-chunk // 32)) * 4 + 16          # LDS of a chunk of the score backward (attn_bwd_lds, encoder_ops.hip)
+    need = chunk * C_ * 2 + chunk * 4 + heads * M * (-(-chunk // 32)) * 4 + 16          # LDS of a chunk of the score backward (attn_bwd_lds, attention.hip)
     assert parts == 9 and need <= 128 * 1024 < need + 2 * C_ * 4
     assert L.crd_attn_bwd_fused_supported(*gap) == 0
     assert L.crd_attn_bwd_fused_supported(1, 8, 4, 5, 104) == 0 and L.crd_attn_scores_bwd_partials(1, 8, 4, 5, 104) > 0      # C = 520

@@ -1,4 +1,4 @@
-"""Every launch path of the encoder attention kernels (camradepth_amd/csrc/encoder_ops.hip, crd_attn_out_residual_stats in norm.hip)
+"""Every launch path of the encoder attention kernels (camradepth_amd/csrc/attention.hip, crd_attn_out_residual_stats in norm.hip)
 against float64 references on the CPU, through the C ABI.
 
 The launchers pick a kernel's geometry from the problem size and the developer switches are read once, so a path is reached by
@@ -102,6 +102,18 @@ def run_scores(q, k, heads, d, scale):
     return qd, kd, S, idx, ii
 
 
+def score_bwd_ref(q, k, ii, dS, heads, d, scale):
+    """float64 scatter reference of the score backward from the kernel's own idx (ii, on the host): dq [B][N][C] and dk [B][M][C]."""
+    B, N, C_ = q.shape
+    M = k.shape[1]
+    gq = (scale * dS.double()).view(B, 1, N, 1)
+    dq_ref = (gq * gather_keys(k, ii, heads, d)).permute(0, 2, 1, 3).reshape(B, N, C_)
+    src = gq * q.double().view(B, N, heads, d).permute(0, 2, 1, 3)                # [B,h,N,d]
+    row = (torch.arange(B * heads).view(B, heads, 1) * M + ii.permute(0, 2, 1)).reshape(-1)
+    dk_ref = torch.zeros(B * heads * M, d, dtype=torch.float64).index_add_(0, row, src.reshape(-1, d))
+    return dq_ref, dk_ref.view(B, heads, M, d).permute(0, 2, 1, 3).reshape(B, M, C_)
+
+
 @pytest.mark.parametrize("shape", list(SCORE_BWD_CASES), ids=lambda s: "x".join(map(str, s)))
 def test_score_backward_paths(shape):
     lib, lb = L()
@@ -113,13 +125,7 @@ def test_score_backward_paths(shape):
     qd, kd, S, idx, ii = run_scores(q, k, heads, d, scale)
     dS = torch.randn(B, N, generator=g)
     dSc = dS.cuda()
-    # float64 scatter reference from the kernel's own idx
-    gq = (scale * dS.double()).view(B, 1, N, 1)
-    dq_ref = (gq * gather_keys(k, ii, heads, d)).permute(0, 2, 1, 3).reshape(B, N, C_)
-    src = gq * q.double().view(B, N, heads, d).permute(0, 2, 1, 3)                # [B,h,N,d]
-    row = (torch.arange(B * heads).view(B, heads, 1) * M + ii.permute(0, 2, 1)).reshape(-1)
-    dk_ref = torch.zeros(B * heads * M, d, dtype=torch.float64).index_add_(0, row, src.reshape(-1, d))
-    dk_ref = dk_ref.view(B, heads, M, d).permute(0, 2, 1, 3).reshape(B, M, C_)
+    dq_ref, dk_ref = score_bwd_ref(q, k, ii, dS, heads, d, scale)
     # the rank-one vector path that crd_attn_bwd runs in extra workgroups of the same launch
     t = to_grad(torch.randn(B, C_, generator=g)).cuda()
     wd = torch.zeros(C_, C_ + 8, dtype=BF16, device="cuda")

@@ -1,10 +1,13 @@
-"""crd_attn_bwd_fused and crd_attn_dk_fold (camradepth_amd/csrc/encoder_ops.hip) against the launches they replace and against float64.
+"""crd_attn_bwd_fused and crd_attn_dk_fold (camradepth_amd/csrc/attention.hip) against the launches they replace and against float64.
 
 The fused launch runs crd_attn_out_bwd(_gn) and the partial form of crd_attn_scores_bwd as one workgroup-local pass: dx1, dS, dq and
 the dK partials must be the SAME BITS as the pair's; t and dbp_rows are fixed-point sums of float partial sums over other pixel chunks
 and are held to the float64 reference with the tolerance tests/test_gpu_attention.py uses for them (rel = elem = 1e-4), and to the
 pair's values with the tolerance that file uses between two forms of one computation (rel = elem = 1e-5: tighter than either form's
-bound against the reference).  Problem builders and references come from tests/test_gpu_attention.py; outputs are pre-filled with NaN."""
+bound against the reference).  Both forms run the same index / row / scatter functions and copies of one text otherwise, so equal bits alone would not
+catch an error the two have in common: the fused form's dS, dq, the sum of its dK partials and the dK that crd_attn_dk_fold makes of them are held to float64 as
+well, with the tolerances tests/test_gpu_attention.py puts on the pair's.  Problem builders and references come from
+tests/test_gpu_attention.py; outputs are pre-filled with NaN."""
 import dataclasses
 
 import pytest
@@ -12,7 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.test_attn_paths_cpu import score_bwd_class
-from tests.test_gpu_attention import BF16, f32, nans, out_problem, refused, run_scores, same_bits, score_problem
+from tests.test_gpu_attention import BF16, bf64, f32, nans, out_problem, refused, run_scores, same_bits, score_bwd_ref, score_problem
 from tests.test_gpu_igemm import assert_close
 from tests.test_gpu_ops import L, P, ok
 from tests.util import gval, to_grad, zsum
@@ -36,9 +39,10 @@ def attention_problem(shape, seed):
     B, N, M, heads, d = shape
     C_, scale = heads * d, f32(d ** -0.5)
     _, q, k = score_problem(B, N, M, heads, d, seed=seed)
-    qd, kd, _, idx, _ = run_scores(q, k, heads, d, scale)
+    qd, kd, _, idx, ii = run_scores(q, k, heads, d, scale)
     g, x, u, S, _, _ = out_problem(B, N, C_, seed=seed + 1)
     p = dict(B=B, N=N, M=M, heads=heads, d=d, C=C_, scale=scale, q=qd, k=kd, idx=idx, x=x, u=u, S=S, xc=x.cuda(), uc=u.cuda(), Sc=S.cuda())
+    p["q_host"], p["k_host"], p["idx_host"] = q, k, ii
     p["dx1"] = torch.randn(B, N, C_, generator=g)
     p["dp"] = torch.tensor([1.0 / 0.9, 0.0, 1.0, 0.7])[torch.arange(B) % 4]
     p["gamma"], p["beta"] = 1 + 0.1 * torch.randn(C_, generator=g), 0.1 * torch.randn(C_, generator=g)
@@ -85,7 +89,13 @@ def run_forms(p, parts_n, pre, dp, dgam, want_ds):
                 ok(lb.crd_attn_out_bwd(P(dx), P(p["uc"]), P(p["Sc"]), P(dpc), B, N, C_, P(t), P(dbp), P(dS), lib.stream()), "attn_out_bwd")
             ok(lb.crd_attn_scores_bwd(P(p["q"]), P(p["k"]), P(dS), P(p["idx"]), B, N, M, heads, d, scale, P(dq), None, P(parts),
                                       lib.stream()), "attn_scores_bwd partials")
-        out.append(dict(dx=dx.cpu(), t=gval(t), dbp=gval(dbp), dS=None if dS is None else dS.cpu(), dq=dq.cpu(), parts=parts.cpu(),
+        dk = None
+        if fused:       # the fold this form continues with (its vector-path riders: tests further down)
+            dk, tb, es = nans(B, M, C_, dtype=BF16), nans(B, C_, dtype=BF16), nans(B, C_)
+            ok(lb.crd_attn_dk_fold(P(parts), parts_n, B * M * C_, P(dk), B * M * C_, P(t), P(p["wd"]), B, C_, C_ + 8, f32(1.0 / N), P(tb), P(es),
+                                   lib.stream()), "attn_dk_fold")
+            dk = dk.float().cpu()
+        out.append(dict(dx=dx.cpu(), t=gval(t), dbp=gval(dbp), dS=None if dS is None else dS.cpu(), dq=dq.cpu(), parts=parts.cpu(), dk=dk,
                         dg=None if dg is None else dg.cpu(), db=None if db is None else db.cpu()))
     return out
 
@@ -99,6 +109,7 @@ def test_fused_launch_equals_the_pair(shape):
     assert lb.crd_attn_bwd_fused_supported(*shape) == parts_n
     p = attention_problem(shape, seed=21)
     C_ = p["C"]
+    p["wd"] = torch.zeros(C_, C_ + 8, dtype=BF16, device="cuda")          # (the riders of crd_attn_dk_fold need a weight)
     can_pre = C_ % 16 == 0
     if can_pre:
         p["gn"] = groupnorm_sums(p)
@@ -134,6 +145,14 @@ def test_fused_launch_equals_the_pair(shape):
                         assert_close(o["dbp"], dbp_ref, f"dbp rows ({form}, {what})", rel=1e-4, elem=1e-4)
                     assert_close(b["t"], a["t"], f"t, fused against the pair ({what})", rel=1e-5, elem=1e-5)
                     assert_close(b["dbp"], a["dbp"], f"dbp rows, fused against the pair ({what})", rel=1e-5, elem=1e-5)
+                    # the fused form against float64: dS of the dx1 it stored, then the scatter of scale * dS through its idx
+                    dS_ref = (dy * p["u"].double().unsqueeze(1)).sum(2)
+                    dq_ref, dk_ref = score_bwd_ref(p["q_host"], p["k_host"], p["idx_host"], dS_ref, heads, d, p["scale"])
+                    if want_ds:
+                        assert_close(b["dS"], dS_ref, f"dS (fused, {what})", rel=1e-4, elem=1e-4)
+                    assert_close(b["dq"].float(), dq_ref, f"dq (fused, {what})")
+                    assert_close(b["parts"].double().sum(0), dk_ref, f"dk = sum of the partial copies (fused, {what})", rel=1e-4, elem=1e-4)
+                    assert_close(b["dk"], bf64(dk_ref), f"dk from crd_attn_dk_fold (fused, {what})", rel=4e-3, elem=1e-2)
                     if dgam:        # the same integer sums added to the same start
                         assert same_bits(b["dg"], a["dg"]) and same_bits(b["db"], a["db"]), f"dgamma / dbeta ({what})"
                         assert_close(b["dg"], dg_ref, f"dgamma ({what})", rel=1e-3, elem=2e-3)
