@@ -1,5 +1,6 @@
 """What the radar and lidar front ends and the point-cloud back end share on the Python side: the argument checks, the geometry of the
-maps, the workspace of the z-buffer rasteriser and the checks of a rasterising call (radar.py, lidar.py, cloud.py)."""
+maps, the workspace of the z-buffer rasteriser and the checks of a rasterising call (radar.py, lidar.py, cloud.py), and the three forms
+of a point cloud that the back ends behind it take (bev.py, occupancy.py)."""
 import torch
 
 from . import lib as L
@@ -23,6 +24,35 @@ def _frames(frame_offsets):
     if off.shape[0] < 2:
         raise L.CrdError("frame_offsets must hold B + 1 >= 2 entries")
     return off, off.shape[0] - 1
+
+
+def _rows(fn, cloud, frame_offsets, valid, labels):
+    """-> (xyz [n,3], valid, labels, frame_offsets or None, rows_per_frame, B) from one of the three forms of the first argument."""
+    if isinstance(cloud, dict):
+        if frame_offsets is not None:
+            raise L.CrdError(f"{fn}: a cloud dictionary brings its own frames; frame_offsets= goes with a bare [n,3] tensor")
+        if "xyz" in cloud and "frame_offsets" in cloud:                       # point_cloud's
+            xyz = _dev(cloud["xyz"], torch.float32, (None, 3), "cloud['xyz']")
+            off, B = _frames(cloud["frame_offsets"])
+            labels = cloud.get("label") if labels is None else labels
+            return xyz, valid, labels, off, 0, B
+        if "points" in cloud and "valid" in cloud:                            # unproject_depth's
+            pts = _dev(cloud["points"], torch.float32, (None, None, None, 3), "cloud['points']")
+            B, h, w, _ = pts.shape
+            if B * h * w == 0:
+                raise L.CrdError(f"{fn}: cloud['points'] holds no pixel")
+            if valid is not None:
+                raise L.CrdError(f"{fn}: an organised cloud brings its own valid")
+            own = _dev(cloud["valid"], torch.uint8, (B, h, w), "cloud['valid']")
+            if labels is not None:
+                labels = _dev(labels, torch.uint8, (B, h, w), "labels").view(-1)          # the label map the cloud was made with
+            return pts.view(-1, 3), own.view(-1), labels, None, h * w, B
+        raise L.CrdError(f"{fn}: a cloud dictionary holds 'xyz' and 'frame_offsets' (point_cloud) or 'points' and 'valid' (unproject_depth)")
+    xyz = _dev(cloud, torch.float32, (None, 3), "xyz")
+    if frame_offsets is None:
+        raise L.CrdError(f"{fn}: a bare xyz tensor needs frame_offsets (int32 [B+1] on the device)")
+    off, B = _frames(frame_offsets)
+    return xyz, valid, labels, off, 0, B
 
 
 def _intrinsics(K, B):

@@ -11,7 +11,7 @@ import torch
 
 from . import lib as L
 from . import viz
-from ._frontend import _dev, _frames
+from ._frontend import _dev, _rows
 
 OPTIONAL = ("z_min", "top_index", "occupancy")
 GRID_OPTIONS = {"x_range": (0.0, 80.0), "y_range": (-40.0, 40.0), "cell": 0.5, "z_range": (-math.inf, math.inf), "min_points": 1,
@@ -69,35 +69,6 @@ class BevWorkspace:
     @property
     def out(self):
         return self.outputs()
-
-
-def _rows(fn, cloud, frame_offsets, valid, labels):
-    """-> (xyz [n,3], valid, labels, frame_offsets or None, rows_per_frame, B) from one of the three forms of the first argument."""
-    if isinstance(cloud, dict):
-        if frame_offsets is not None:
-            raise L.CrdError(f"{fn}: a cloud dictionary brings its own frames; frame_offsets= goes with a bare [n,3] tensor")
-        if "xyz" in cloud and "frame_offsets" in cloud:                       # point_cloud's
-            xyz = _dev(cloud["xyz"], torch.float32, (None, 3), "cloud['xyz']")
-            off, B = _frames(cloud["frame_offsets"])
-            labels = cloud.get("label") if labels is None else labels
-            return xyz, valid, labels, off, 0, B
-        if "points" in cloud and "valid" in cloud:                            # unproject_depth's
-            pts = _dev(cloud["points"], torch.float32, (None, None, None, 3), "cloud['points']")
-            B, h, w, _ = pts.shape
-            if B * h * w == 0:
-                raise L.CrdError(f"{fn}: cloud['points'] holds no pixel")
-            if valid is not None:
-                raise L.CrdError(f"{fn}: an organised cloud brings its own valid")
-            own = _dev(cloud["valid"], torch.uint8, (B, h, w), "cloud['valid']")
-            if labels is not None:
-                labels = _dev(labels, torch.uint8, (B, h, w), "labels").view(-1)          # the label map the cloud was made with
-            return pts.view(-1, 3), own.view(-1), labels, None, h * w, B
-        raise L.CrdError(f"{fn}: a cloud dictionary holds 'xyz' and 'frame_offsets' (point_cloud) or 'points' and 'valid' (unproject_depth)")
-    xyz = _dev(cloud, torch.float32, (None, 3), "xyz")
-    if frame_offsets is None:
-        raise L.CrdError(f"{fn}: a bare xyz tensor needs frame_offsets (int32 [B+1] on the device)")
-    off, B = _frames(frame_offsets)
-    return xyz, valid, labels, off, 0, B
 
 
 def bev_grid(cloud_or_xyz, frame_offsets=None, x_range=(0, 80), y_range=(-40, 40), cell=0.5, z_range=(-math.inf, math.inf), min_points=1,

@@ -1,6 +1,6 @@
 """Raw sensors to depth, point cloud and pictures in ONE captured graph: the camera front end, the radar front end, the input
-assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid behind it, if asked for) and the visualiser
-on static buffers, replayed once per frame.
+assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid and the occupancy map behind it, if asked
+for) and the visualiser on static buffers, replayed once per frame.
 
 Each stage exists on its own (camera.camera_inputs, radar.radar_inputs, batch.assemble_batch, inference.InferenceGraph,
 cloud.point_cloud, viz.Visualizer) and LivePipeline.run returns the bits of calling them one by one; what it adds is the ownership of
@@ -11,6 +11,7 @@ import math
 import torch
 
 from . import lib as L
+from . import occupancy as occ
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
 from .cloud import CloudWorkspace, point_cloud
@@ -20,6 +21,9 @@ from .viz import Visualizer
 
 CLOUD_OPTIONS = {"stride": 1, "min_range": 0.0, "max_range": math.inf, "max_depth": 100.0, "rgb": False, "pixel": False}
 BEV_OPTIONS = dict(GRID_OPTIONS, picture=False, picture_z_range=(-2.0, 4.0), cmap="jet")
+# the map's own options (OccupancyMap), M (None: one map per frame; 1: the frames are the cameras of one rig), centre (None: the
+# camera; or a point of the out frame the window is centred on, such as (20, 0, 0)) and picture (True: also occupancy.picture in cmap)
+OCCUPANCY_OPTIONS = dict(occ.MAP_OPTIONS, nx=160, ny=160, cell=0.5, M=None, centre=None, picture=False, cmap="jet")
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -45,16 +49,24 @@ class LivePipeline:
     cloud: None, or a dictionary of point_cloud's stride, min_range, max_range, max_depth, rgb (colours from the image) and pixel.
     bev: None, or a dictionary of bev_grid's x_range, y_range, cell, z_range, min_points and flip, and picture (True: also the height
     map in colours, bev.picture over picture_z_range in cmap).  It needs cloud=: the grid is laid in the cloud's frame, out_from_cam.
+    occupancy: None, or a dictionary of OCCUPANCY_OPTIONS: an OccupancyMap (`occupancy_map`, owned by this object) fused over the runs,
+    fed from the cloud with the pose run(map_from_out=) brings.  It needs cloud=; the camera's position in the cloud's frame is the
+    sensor.  The map is empty after construction; occupancy_map.reset() empties it again.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, bev_grid [, bev.picture], Visualizer.render."""
+    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None):
+                 bev=None, occupancy=None):
         fn = "LivePipeline"
+        if occupancy is not None:
+            if cloud is None:
+                raise L.CrdError(f"{fn}: occupancy= needs cloud= (the map is fed from the point cloud)")
+            if not isinstance(occupancy, dict) or not set(occupancy) <= set(OCCUPANCY_OPTIONS):
+                raise L.CrdError(f"{fn}: occupancy= holds {sorted(OCCUPANCY_OPTIONS)}, not {occupancy!r}")
         if bev is not None:
             if cloud is None:
                 raise L.CrdError(f"{fn}: bev= needs cloud= (the grid is made from the point cloud, in its frame)")
@@ -113,6 +125,24 @@ class LivePipeline:
             self.bev_ws = BevWorkspace(B, nx, ny, device=dev)
             self.bev_out = self.bev_ws.outputs()
             self.bev_picture = torch.empty(B, nx, ny, 3, dtype=torch.uint8, device=dev) if o["picture"] else None
+        self.occupancy_opts = None if occupancy is None else dict(OCCUPANCY_OPTIONS, **occupancy)
+        self.occupancy_map = None
+        if self.occupancy_opts is not None:
+            o = self.occupancy_opts
+            self.occupancy_map = occ.OccupancyMap(B if o["M"] is None else o["M"], o["nx"], o["ny"], o["cell"], device=dev,
+                                                  **{k: o[k] for k in occ.MAP_OPTIONS})
+            self.occupancy_ws = occ.OccupancyWorkspace(self.occupancy_map, B)
+            self.map_from_out = self.camera_frame.clone()
+            self.sensor = torch.zeros(B, 3, dtype=torch.float64, device=dev)
+            try:
+                centre = None if o["centre"] is None else [float(v) for v in o["centre"]]
+            except (TypeError, ValueError):
+                centre = ()
+            if centre is not None and len(centre) != 3:
+                raise L.CrdError(f"{fn}: occupancy centre {o['centre']!r} is three numbers")
+            self.centre = None if centre is None else torch.tensor(centre, dtype=torch.float64, device=dev)
+            M = self.occupancy_map.M
+            self.occupancy_picture = torch.empty(M, o["nx"], o["ny"], 3, dtype=torch.uint8, device=dev) if o["picture"] else None
         self.visualizer = None if viz is None else Visualizer(B, h, w, **dict({"image_order": order_out, "device": dev}, **viz))
         # the eval plan, exactly as InferenceGraph takes it
         was_training = model.training
@@ -131,6 +161,9 @@ class LivePipeline:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=self.stream):
                 self._results = self._stages(pack=False)
+            if self.occupancy_map is not None:      # the warm-up pass fused a frame of zeros into the map: the first run starts empty
+                self.occupancy_map.reset()
+                self.occupancy_map.status_word.zero_()
         torch.cuda.current_stream().wait_stream(self.stream)
         model.train(was_training)
 
@@ -172,6 +205,12 @@ class LivePipeline:
                 out["bev"] = dict(grid)
                 if self.bev_picture is not None:
                     out["bev"]["picture"] = picture(grid, o["picture_z_range"], o["cmap"], out=self.bev_picture)
+            if self.occupancy_map is not None:
+                res = occ.update(self.occupancy_map, out["cloud"], map_from_points=self.map_from_out, sensor=self.sensor, centre=self.centre,
+                                 workspace=self.occupancy_ws, out=self.occupancy_ws.out)
+                out["occupancy"] = dict(res)
+                if self.occupancy_picture is not None:
+                    out["occupancy"]["picture"] = occ.picture(res, self.occupancy_map, self.occupancy_opts["cmap"], out=self.occupancy_picture)
         if self.visualizer is not None:
             out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
         return out
@@ -190,18 +229,21 @@ class LivePipeline:
         dst.copy_(value)
 
     def run(self, frames, points=None, sweep_index=None, frame_offsets=None, cam1_from_sensor=None, cam2_from_sensor=None, lags=None, K=None,
-            out_from_cam=None, clone=False):
+            out_from_cam=None, clone=False, map_from_out=None):
         """One batch of sensor data through the graph.
 
         frames: uint8 [B,H,W,frame_channels] with any strides (a view of a capture buffer; a host tensor is copied up).  points
         [n,5], sweep_index [n], frame_offsets [B+1], cam1_from_sensor / cam2_from_sensor [S,3,4], lags [S,2]: radar_inputs' arguments
         with n <= max_points and S <= max_sweeps, frame_offsets ending at or below n; a 3-channel model takes none of them.  K: fp64
         [3,3] or [B,3,3], the camera's intrinsics at full resolution (the radar projection and the cloud read it; an RGB-only pipeline
-        without a cloud needs none).  out_from_cam: fp64 [3,4] or [B,3,4], the cloud's frame; None: the camera's own.
+        without a cloud needs none).  out_from_cam: fp64 [3,4] or [B,3,4], the cloud's frame; None: the camera's own.  map_from_out:
+        fp64 [3,4] or [B,3,4], the pose of the cloud's frame in the occupancy map's frame for this batch (with occupancy= only); None:
+        the identity.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev' and 'pictures' (if asked for at construction: the dictionaries of point_cloud, of bev_grid
-        -- with 'picture' if asked for -- and of Visualizer.render).  They are VIEWS of this object's static buffers, valid until the
+        output dictionary), 'cloud', 'bev', 'occupancy' and 'pictures' (if asked for at construction: the dictionaries of point_cloud,
+        of bev_grid and of occupancy.update -- each with 'picture' if asked for -- and of Visualizer.render).  They are VIEWS of this
+        object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call
         does not wait for the device."""
         self._load(self.frames, frames, "frames")
@@ -225,6 +267,15 @@ class LivePipeline:
         else:
             self._load(self.out_from_cam, out_from_cam.expand(self.B, 3, 4) if torch.is_tensor(out_from_cam) and
                        tuple(out_from_cam.shape) == (3, 4) else out_from_cam, "out_from_cam")
+        if self.occupancy_map is not None:
+            self.sensor.copy_(self.out_from_cam[:, :, 3])                     # the camera's position in the cloud's frame
+            if map_from_out is None:
+                self.map_from_out.copy_(self.camera_frame)
+            else:
+                self._load(self.map_from_out, map_from_out.expand(self.B, 3, 4) if torch.is_tensor(map_from_out) and
+                           tuple(map_from_out.shape) == (3, 4) else map_from_out, "map_from_out")
+        elif map_from_out is not None:
+            raise L.CrdError("LivePipeline.run: map_from_out goes with occupancy=")
         self.plan.ensure_packed()                   # optimizer step / load_state_dict / mark_params_changed() since the last frame
         self.graph.replay()
         return _copies(self._results) if clone else dict(self._results)

@@ -891,6 +891,83 @@ int crd_bev_grid(const float* xyz, const uint8_t* valid, const uint8_t* label, c
                  float* z_min, int32_t* top_index, uint8_t* top_label, uint8_t* occupancy, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Occupancy map: point clouds -> free / occupied / unknown per cell, fused over frames in a world-aligned rolling window
+ * ("Occupancy map").  The step after the bird's-eye-view grid, with its conventions: fp64 arithmetic, fp64 quantities
+ * through device memory or as IEEE-754 bit patterns, no allocation, no synchronisation, capturable in a graph on one stream, arguments
+ * checked before any GPU call.  The entry adds no struct and changes no signature: CRD_ABI_VERSION stays.  Only IEEE add, multiply,
+ * divide, floor and compare are used, every operation rounded on its own; tests/occupancy_ref.py restates them in NumPy and the
+ * kernels agree with it bit for bit.
+ *
+ * The map.  M maps of nx x ny cells of `cell` metres, axes those of the map frame (a fixed world or odometry frame).  World cell
+ * (wx, wy) covers wx * cell <= X < (wx + 1) * cell and wy * cell <= Y < (wy + 1) * cell; it lives in slot [m][wx mod nx][wy mod ny]
+ * (the mathematical modulo, 0 .. nx - 1 for negative wx as well) of `map`, int16 [M][nx][ny]: a torus.  The window of map m covers the
+ * world cells ox <= wx < ox + nx, oy <= wy < oy + ny with (ox, oy) = cur_origin[m]; prev_origin[m] is the window of the update before.
+ * The window moves by whole cells; nothing is resampled or copied.  State of the caller, on the device, read and written by the kernels:
+ * map; prev_origin and cur_origin, int64 [M][2]; initialised, int32 [M] (0: the map holds nothing yet, whatever its memory holds --
+ * filling it with 0 resets the map); status, int32 [M], bits that are only ever set (1: an update of the map was skipped, 2: a frame
+ * that feeds it had a sensor position that is not finite).
+ *
+ * Rows: xyz, valid, frame_offsets, rows_per_frame, B, n_rows exactly as for crd_bev_grid.  map_from_points: fp64 [3][4] row-major, one
+ * for all frames (t_stride 0) or one per frame (t_stride 12), or NULL: the identity.  sensor, centre: fp64 [3], one for all frames
+ * (stride 0) or one per frame (stride 3), IN THE POINTS' FRAME; sensor NULL: the origin; centre NULL: the sensor.  M == B: frame b
+ * feeds map b; M == 1: every frame feeds map 0 (the cameras of one rig) and its centre is frame 0's.
+ * With T the frame's matrix, "T . (x, y, z)" is X = T[0][0] * x + T[0][1] * y + T[0][2] * z + T[0][3] summed left to right, Y from
+ * row 1, Z from row 2; T NULL: (x, y, z) itself.  S_b = T_b . sensor_b;  C_m = T_b . centre_b with b = m (M == B) or 0 (M == 1).
+ *
+ * The bin of a direction (dx, dy), not both zero, with q_bins = n_bins / 4 (four faces of a square, q_bins bins along each):
+ *   |dx| >= |dy|:  face = 0 if dx > 0 else 2,  s = dy / |dx|;      otherwise:  face = 1 if dy > 0 else 3,  s = dx / |dy|
+ *   q = min(floor(((s + 1.0) * 0.5) * q_bins), q_bins - 1);   k = face * q_bins + q
+ *
+ * Launch 1, prepare.  hit_min[b][k] = the bits of +inf and seen_max[b][k] = 0 for every frame and bin; hits[m][i][j] = 0 for every
+ * window cell; S_b for every frame (status bit 2 of its map when a component is not finite); per map: fx = floor(Cx / cell),
+ * fy = floor(Cy / cell); the update of the map is SKIPPED when Cx, Cy or Cz is not finite or |fx| or |fy| >= 2^31 - 65536: status bit
+ * 1, the origins stay; otherwise prev_origin = cur_origin, then cur_origin = (fx - nx / 2, fy - ny / 2) with the integer quotient.
+ * Launch 2, points (left out with n_rows == 0).  Row p of frame b, (x, y, z) its floats converted to fp64, m its map:
+ *   1. skipped when valid != NULL and valid[p] == 0, or when it has no frame
+ *   2. (X, Y, Z) = T_b . (x, y, z); skipped unless X, Y, Z and the three components of S_b are finite
+ *   3. dx = X - Sx, dy = Y - Sy, r2 = dx * dx + dy * dy; skipped when r2 == 0 or r2 > max_range * max_range; k = the bin of (dx, dy)
+ *   4. seen, if z_floor <= Z <= z_hi:  seen_max[b][k] = max(seen_max[b][k], bits(r2))     as unsigned 64-bit integers
+ *   5. hit, if z_lo <= Z <= z_hi:      hit_min[b][k] = min(hit_min[b][k], bits(r2)), and with wx = floor(X / cell), wy = floor(Y / cell),
+ *      if ox <= wx < ox + nx and oy <= wy < oy + ny, compared as doubles, (ox, oy) = cur_origin[m]:  hits[m][wx - ox][wy - oy] += 1
+ * Launch 3, cells.  Window cell (m, i, j) is world cell (wx, wy) = (ox + i, oy + j) in slot (wx mod nx, wy mod ny);
+ *   old = the slot's value if initialised[m] was nonzero before the call and the world cell lies in the prev_origin window, else 0
+ *   evidence = 2 if hits[m][i][j] >= min_points;  otherwise 1 if for ANY frame b that feeds the map, with cx = (wx + 0.5) * cell,
+ *     cy = (wy + 0.5) * cell (wx, wy converted to fp64), dx = cx - Sx, dy = cy - Sy, r2c = dx * dx + dy * dy and k the bin of (dx, dy):
+ *       r2c > 0  and  r2c < hit_min[b][k]  and  r2c <= seen_max[b][k]           (the keys read back as doubles; a frame whose S_b is
+ *     not finite fails the first); otherwise 0.  The centre is nearer than the first obstacle on its bearing and no farther than
+ *     something seen there.  (seen_max <= max_range * max_range, so the kernel may test r2c against that before it takes the bin.)
+ *   new = min(max(old + (l_occ, -l_free, 0 for evidence 2, 1, 0), -l_max), l_max)    in integers
+ *   the slot = new (each slot belongs to exactly one window cell); initialised[m] = 1
+ *   a skipped map: evidence = 0 and new = old at the window it had, with old = the slot's value if initialised[m] was nonzero, else
+ *   0; neither the slot nor initialised[m] is written.
+ * Outputs in WINDOW order, [M][nx][ny], written in full: log_odds int16 = new; state uint8 = 2 if new >= occupied_at, 1 if
+ * new <= -free_at, else 0; evidence uint8; value fp32 = (float)new (may be NULL); origin int64 [M][2] = cur_origin after launch 1.
+ *
+ * The same bits every run: only integer minimum, maximum, add and or, whose results do not depend on the order of arrival
+ * (non-negative doubles order as their bit patterns).  No workgroup waits for another.  A key atomic is skipped where a plain read
+ * already settles it; rows of neighbouring lanes of a wave that share a bin, or hit the same cell, are folded first and issue one set
+ * of atomics, which changes no result.
+ * workspace, 16-byte aligned, each part from the next multiple of 16 bytes: hit_min uint64 [B][n_bins]; seen_max uint64 [B][n_bins];
+ * S fp64 [B][3]; hits int32 [M][nx][ny]; the maps' flags of this call int32 [M]:
+ *   workspace_bytes >= 2 * ((8 * B * n_bins + 15) & ~15) + ((24 * B + 15) & ~15) + ((4 * M * nx * ny + 15) & ~15) + ((4 * M + 15) & ~15).
+ * CRD_E_INVALID, nothing launched: NULL workspace, map, prev_origin, cur_origin, initialised, status, log_odds, state, evidence or
+ * origin, NULL xyz with n_rows > 0; xyz, frame_offsets, initialised, status or value not 4-byte aligned, map or log_odds not 2-byte,
+ * map_from_points, sensor, centre or an origin not 8-byte, the workspace not 16-byte aligned; B <= 0; n_rows < 0; M neither B nor 1;
+ * nx or ny outside 1 .. 65535; M * nx * ny >= 2^31; n_bins not a multiple of 4 in 4 .. 65536; cell not finite and positive;
+ * max_range not positive or its square not finite; a NaN z bound or not z_floor <= z_lo <= z_hi; t_stride not 0 or 12; sensor_stride
+ * or centre_stride not 0 or 3; both or neither of frame_offsets and rows_per_frame; min_points < 1; not 1 <= l_occ, l_free <= l_max
+ * <= 32767; occupied_at or free_at outside 1 .. l_max; a workspace too small.
+ * ------------------------------------------------------------------------------------------- */
+int crd_occupancy_update(const float* xyz, const uint8_t* valid, const int32_t* frame_offsets, int32_t rows_per_frame, int32_t B,
+                         int32_t n_rows, const double* map_from_points, int32_t t_stride, const double* sensor, int32_t sensor_stride,
+                         const double* centre, int32_t centre_stride, int32_t M, int32_t nx, int32_t ny, uint64_t cell_f64_bits,
+                         int32_t n_bins, uint64_t max_range_f64_bits, uint64_t z_floor_f64_bits, uint64_t z_lo_f64_bits,
+                         uint64_t z_hi_f64_bits, int32_t min_points, int32_t l_occ, int32_t l_free, int32_t l_max, int32_t occupied_at,
+                         int32_t free_at, int16_t* map, int64_t* prev_origin, int64_t* cur_origin, int32_t* initialised, int32_t* status,
+                         void* workspace, int64_t workspace_bytes, int16_t* log_odds, uint8_t* state, uint8_t* evidence, float* value,
+                         int64_t* origin, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
