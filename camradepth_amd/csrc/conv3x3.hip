@@ -319,16 +319,22 @@ extern "C" int crd_tune_conv3x3_small_grid(int workgroups) {
   return old;
 }
 
-// Called from crd_conv_igemm for 3x3 / stride 1 / pad 1 layers on grids large enough to fill the chip.
-int crd_conv3x3_halo(const ConvK& k, int B, hipStream_t st, long long partial_cap) {
+// Does crd_conv3x3_halo send this launch to the persistent one-wave-per-SIMD kernel (conv3x3p.hip)?  One rule for the launch below
+// and for crd_conv_igemm_route (igemm.hip).
+bool crd_conv3x3_halo_persistent(const ConvK& k, int B, long long partial_cap) {
   // persistent one-wave-per-SIMD kernel (conv3x3p.hip) for the 128-column tiles (96 / 64 columns: one narrower tile).  Its
   // GroupNorm sums need the caller's partial-sum buffer; without one (or a too small one) the launch stays here.
   // (a launch WITH GroupNorm sums whose column count leaves a ragged tail of <= 64 columns -- e.g. Cout 160 / 192 / 288; no
   // layer of the model -- would need its sums split over two kernels: it stays with the two-workgroup kernel below)
   const int rest128 = k.Cout > 96 ? k.Cout % 128 : 0;
   const bool ragged_stats = k.stats && rest128 > 0 && rest128 <= 64;
-  if (crd_conv3x3p_applicable(k, B) && !ragged_stats &&
-      (!k.stats || (k.stats_partial && crd_conv3x3p_partial_floats(k, B) <= partial_cap))) {
+  return crd_conv3x3p_applicable(k, B) && !ragged_stats &&
+         (!k.stats || (k.stats_partial && crd_conv3x3p_partial_floats(k, B) <= partial_cap));
+}
+
+// Called from crd_conv_igemm for 3x3 / stride 1 / pad 1 layers on grids large enough to fill the chip.
+int crd_conv3x3_halo(const ConvK& k, int B, hipStream_t st, long long partial_cap) {
+  if (crd_conv3x3_halo_persistent(k, B, partial_cap)) {
     // a ragged tail of <= 64 columns (data gradients towards 136 / 144 / 296 / 304 channels) goes to the narrow tiles here
     const int N = k.Cout;
     int rc;

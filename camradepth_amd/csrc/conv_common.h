@@ -63,9 +63,15 @@ inline void convk_from_desc(const crd_conv_desc& d, ConvK& k) {
 }
 
 
-// fp32 LDS-staged epilogue (conv_epilogue's second branch) applies?  One definition for conv_epilogue and conv_epilogue_idle.
+// Which of conv_epilogue's three branches a launch takes: the bf16 vector path, the fp32 LDS-staged path, or (neither) the per-lane
+// scalar path.  One definition each for conv_epilogue, conv_epilogue_idle and the host (crd_conv_igemm_route names the branch from
+// the same expressions, on the argument block exactly as the launch would pass it).
+__host__ __device__ __forceinline__ bool conv_use_vec(const ConvK& a) {
+  return (a.out_mode == 0 || (a.patch_c & 7) == 0) && !a.y_f32 && !a.res && (a.Cout & 7) == 0 && (a.y_ld & 7) == 0 && a.vec_ok;
+}
+// fp32 LDS-staged epilogue (conv_epilogue's second branch) applies?
 template <int BM, int BN, int NT>
-__device__ __forceinline__ bool conv_use_vecf(const ConvK& a) {
+__host__ __device__ __forceinline__ bool conv_use_vecf(const ConvK& a) {
   return a.vecf_ok && a.out_mode == 0 && a.y_f32 && !a.stats_partial && (NT % (BN / 4) == 0) &&
          (size_t)BM * (BN + 4) * 4 + (size_t)NT * 8 * 4 <= (size_t)a.lds_bytes;
 }
@@ -87,7 +93,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& a, f32x16 (&acc)[TM][
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64, LDT = BN + 8, BMH = BM / HALVES;
   static_assert(HALVES == 1 || (HALVES == 2 && WM % 2 == 0), "row halves are whole waves");
   float* red = reinterpret_cast<float*>(smem) + (BMH * LDT) / 2;     // behind the bf16 staging tile
-  const bool vec = (a.out_mode == 0 || (a.patch_c & 7) == 0) && !a.y_f32 && !a.res && (a.Cout & 7) == 0 && (a.y_ld & 7) == 0 && a.vec_ok;
+  const bool vec = conv_use_vec(a);
   if (vec) {
     bf16_t* T = reinterpret_cast<bf16_t*>(smem);
     bf16_t* yb = reinterpret_cast<bf16_t*>(a.y) + (long long)b * a.y_bstride;
@@ -537,7 +543,7 @@ __device__ __forceinline__ void conv_epilogue_reg(const ConvK& a, f32x16& acc, i
 // conv_epilogue: one in the LDS-staged vector path, one before the statistics fold.  Keep in step with conv_epilogue.
 template <int BM, int BN, int NT>
 __device__ __forceinline__ void conv_epilogue_idle(const ConvK& a) {
-  const bool vec = (a.out_mode == 0 || (a.patch_c & 7) == 0) && !a.y_f32 && !a.res && (a.Cout & 7) == 0 && (a.y_ld & 7) == 0 && a.vec_ok;
+  const bool vec = conv_use_vec(a);
   if (!vec && conv_use_vecf<BM, BN, NT>(a)) {      // fp32 staging path: one barrier, three more with statistics
     __syncthreads();
     if (a.stats) { __syncthreads(); __syncthreads(); __syncthreads(); }

@@ -12,6 +12,7 @@
 
 using namespace crdk;
 int crd_conv3x3_halo(const ConvK& k, int B, hipStream_t st, long long partial_cap);   // conv3x3.hip
+bool crd_conv3x3_halo_persistent(const ConvK& k, int B, long long partial_cap);       // ... does it take the persistent kernel (conv3x3p.hip)?
 bool crd_pw_wide_plain_applicable(const ConvK& k);                                      // gngemm.hip: wide pointwise layers
 int crd_pw_wide_plain(const ConvK& k, int B, hipStream_t st);
 
@@ -244,49 +245,141 @@ __global__ __launch_bounds__(256 * KG) void k_igemm(ConvK a) {
 int g_rege_on = 1;
 long long g_rege_launches = 0;
 // bf16 output in the plain layout (what conv_epilogue's vector path covers, minus the patch scatter), no per-tile partial statistics,
-// no per-channel sums; the fused reduce needs whole 16-channel slabs
+// no per-channel sums; the fused reduce needs whole 16-channel slabs.  (A pure predicate: the launch counts, the route query does not.)
 bool crd_igemm_reg_epilogue_applies(const ConvK& k) {
-  const bool ok = g_rege_on && k.out_mode == 0 && !k.y_f32 && !k.res && (k.Cout & 7) == 0 && (k.y_ld & 7) == 0 && k.vec_ok && !k.chan &&
-                  (!k.red_x || ((k.Cout & 15) == 0 && (k.red_x_ld & 7) == 0 && (reinterpret_cast<uintptr_t>(k.red_x) & 15) == 0));
-  if (ok) ++g_rege_launches;
-  return ok;
+  return g_rege_on && k.out_mode == 0 && !k.y_f32 && !k.res && (k.Cout & 7) == 0 && (k.y_ld & 7) == 0 && k.vec_ok && !k.chan &&
+         (!k.red_x || ((k.Cout & 15) == 0 && (k.red_x_ld & 7) == 0 && (reinterpret_cast<uintptr_t>(k.red_x) & 15) == 0));
 }
 
-template <int WM, int WN, int TM, int TN, int MODE, int NST, int KG = 1>
-void launch_mode(const ConvK& k, dim3 grid, hipStream_t st) {
+// ---- one launch, decided once ------------------------------------------------------------------------------------------------
+// What a launch of k_igemm<WM, WN, TM, TN, MODE, NST, KG, REGE> is made of: the argument block as the kernel receives it (n_tiles, the
+// partial-sum buffer or its fallback to atomics, lds_bytes), the grid, the gather MODE and whether the register epilogue runs.
+// crd_conv_igemm launches from it and crd_conv_igemm_route prints it: neither decides anything on its own.
+struct IgemmLaunch {
+  ConvK k;
+  dim3 grid;
+  int mode;        // 0 forward gather, 1 data gradient with stride 1, 2 strided data gradient
+  bool rege;
+  size_t lds;
+};
+
+template <int WM, int WN, int TM, int TN, int NST, int KG>
+IgemmLaunch prepare(const ConvK& k0, int B, long long partial_cap) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  constexpr size_t lds = (size_t)KG * NST * (BM + BN) * BK * sizeof(bf16_t);
-  if (lds > 64 * 1024) crd_reserve_lds_once<&k_igemm<WM, WN, TM, TN, MODE, NST, KG>>((int)lds, "k_igemm");
-  ConvK kk = k;
-  kk.lds_bytes = (int)lds;
+  IgemmLaunch p;
+  p.k = k0;
+  p.k.n_tiles = cdiv(p.k.OHW, BM);
+  if ((long long)B * p.k.n_tiles * p.k.G16 * 2 > partial_cap) p.k.stats_partial = nullptr;
+  p.grid = dim3(p.k.n_tiles, cdiv(p.k.Cout, BN), B);
+  p.mode = p.k.gather_mode == 0 ? 0 : p.k.stride == 1 ? 1 : 2;
+  p.lds = (size_t)KG * NST * (BM + BN) * BK * sizeof(bf16_t);
+  p.rege = TM == 1 && TN == 1 && KG == 1 && WM == 2 && WN == 2 && crd_igemm_reg_epilogue_applies(p.k);
+  p.k.lds_bytes = (int)p.lds;
+  return p;
+}
+
+template <int WM, int WN, int TM, int TN, int MODE, int NST, int KG>
+void launch_mode(const IgemmLaunch& p, hipStream_t st) {
+  if (p.lds > 64 * 1024) crd_reserve_lds_once<&k_igemm<WM, WN, TM, TN, MODE, NST, KG>>((int)p.lds, "k_igemm");
   if constexpr (TM == 1 && TN == 1 && KG == 1 && WM == 2 && WN == 2) {
-    if (crd_igemm_reg_epilogue_applies(k)) {
-      hipLaunchKernelGGL((k_igemm<WM, WN, TM, TN, MODE, NST, KG, true>), grid, dim3(256), lds, st, kk);
+    if (p.rege) {
+      ++g_rege_launches;
+      hipLaunchKernelGGL((k_igemm<WM, WN, TM, TN, MODE, NST, KG, true>), p.grid, dim3(256), p.lds, st, p.k);
       return;
     }
   }
-  hipLaunchKernelGGL((k_igemm<WM, WN, TM, TN, MODE, NST, KG>), grid, dim3(256 * KG), lds, st, kk);
+  hipLaunchKernelGGL((k_igemm<WM, WN, TM, TN, MODE, NST, KG>), p.grid, dim3(256 * KG), p.lds, st, p.k);
 }
 
-template <int WM, int WN, int TM, int TN, int NST, int KG = 1>
+template <int WM, int WN, int TM, int TN, int NST, int KG>
 int launch(const ConvK& k0, int B, hipStream_t st, long long partial_cap) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  ConvK k = k0;
-  k.n_tiles = cdiv(k.OHW, BM);
-  if ((long long)B * k.n_tiles * k.G16 * 2 > partial_cap) k.stats_partial = nullptr;
-  dim3 grid(k.n_tiles, cdiv(k.Cout, BN), B);
-  if (k.gather_mode == 0) launch_mode<WM, WN, TM, TN, 0, NST, KG>(k, grid, st);
-  else if (k.stride == 1) launch_mode<WM, WN, TM, TN, 1, NST, KG>(k, grid, st);
-  else launch_mode<WM, WN, TM, TN, 2, NST, KG>(k, grid, st);
+  const IgemmLaunch p = prepare<WM, WN, TM, TN, NST, KG>(k0, B, partial_cap);
+  if (p.mode == 0) launch_mode<WM, WN, TM, TN, 0, NST, KG>(p, st);
+  else if (p.mode == 1) launch_mode<WM, WN, TM, TN, 1, NST, KG>(p, st);
+  else launch_mode<WM, WN, TM, TN, 2, NST, KG>(p, st);
+  const ConvK& k = p.k;
   if (k.stats && k.stats_partial)
     hipLaunchKernelGGL(k_stats_finalize, dim3(k.G16, B), dim3(256), 0, st, k.stats_partial, k.n_tiles, k.G16, k.stats);
   CRD_LAUNCH_CHECK("crd_conv_igemm");
   return CRD_OK;
 }
 
-}  // namespace
+// The label of the same launch: the instantiation, the branch of the epilogue (conv_common.h: conv_use_vec / conv_use_vecf, the
+// expressions the kernel itself evaluates, on the block the kernel would receive) and how the GroupNorm sums leave the workgroup.
+template <int WM, int WN, int TM, int TN, int NST, int KG>
+int describe(const ConvK& k0, int B, long long partial_cap, char* label, int capacity) {
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  const IgemmLaunch p = prepare<WM, WN, TM, TN, NST, KG>(k0, B, partial_cap);
+  const char* epi = p.rege ? "rege" : conv_use_vec(p.k) ? "vec" : conv_use_vecf<BM, BN, 256>(p.k) ? "vecf" : "scalar";
+  // (the fp32 staged branch adds its sums itself, always with atomics: it is only taken without a partial-sum buffer)
+  const char* sums = !p.k.stats ? "" : p.k.stats_partial ? "+partials" : "+atomics";
+  const int n = snprintf(label, capacity, "k_igemm<%d,%d,%d,%d,MODE=%d,NST=%d,KG=%d>/%s%s", WM, WN, TM, TN, p.mode, NST, KG, epi, sums);
+  CRD_CHECK_ARG(n < capacity, "crd_conv_igemm_route: the label needs %d bytes, capacity is %d", n + 1, capacity);
+  return CRD_OK;
+}
 
-extern "C" int crd_conv_igemm(const crd_conv_desc* d, crd_stream_t stream) {
+// Every instantiation crd_conv_igemm can launch: name, WM, WN, TM, TN, NST, KG.  The launch switch and the label switch are both
+// generated from this list.
+#define CRD_IGEMM_TILES(X)                                                                                             \
+  X(S64_NST2, 2, 2, 1, 1, 2, 1) X(S64_NST3, 2, 2, 1, 1, 3, 1) X(S64_NST4, 2, 2, 1, 1, 4, 1) X(S64_SPLITK4, 2, 2, 1, 1, 2, 4) \
+  X(T128x32, 4, 1, 1, 1, 3, 1) X(T128x64, 2, 2, 2, 1, 3, 1) X(T128x96, 4, 1, 1, 3, 2, 1) X(T128x160, 4, 1, 1, 5, 2, 1)      \
+  X(T128x128, 2, 2, 2, 2, 2, 1)
+
+enum IgemmRoute {
+  ROUTE_HALO3X3, ROUTE_PW_NARROW, ROUTE_PW_WIDE_PLAIN,      // hand-offs to other kernel families (their own tile choice is theirs)
+#define X(name, ...) ROUTE_##name,
+  CRD_IGEMM_TILES(X)
+#undef X
+};
+
+// THE dispatch rule of crd_conv_igemm, for a descriptor that has passed the argument checks (k = convk_from_desc + stats_partial).
+IgemmRoute igemm_route(const crd_conv_desc* d, const ConvK& k) {
+  // 3x3 / stride 1 / pad 1 on grids at least one tile wide: halo-tile kernel (conv3x3.hip)
+  if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->out_mode == 0 && d->IH == d->OH && d->IW == d->OW &&
+      d->IW >= 32 && d->IH >= 8)
+    return ROUTE_HALO3X3;
+  // pointwise layers that are all INPUT (Mlp.fc2 and fc1's data gradient at encoder stages 1-2): weights in registers, rows streamed once
+  if (d->KH == 1 && d->KW == 1 && crd_pw_narrow_applicable(k, nullptr)) return ROUTE_PW_NARROW;
+  // pointwise layers that are all output (fc2's data gradient at encoder stages 1-2): the register-resident-weight kernel
+  if (d->KH == 1 && d->KW == 1 && crd_pw_wide_plain_applicable(k)) return ROUTE_PW_WIDE_PLAIN;
+  {   // developer override of the tile choice below (tools/bench_small_gemm.py sweeps it)
+    static int force = -1;
+    if (force < 0) force = crd_dev_int("CRD_IGEMM_FORCE", 0);
+    switch (force) {
+      case 1: return ROUTE_S64_NST4;
+      case 2: return ROUTE_T128x64;
+      case 3: return ROUTE_T128x128;
+      case 4: return ROUTE_S64_SPLITK4;
+      case 5: return ROUTE_S64_NST3;
+      case 6: return ROUTE_S64_NST2;
+      default: break;
+    }
+  }
+  // small problems: 64x64 tiles so that the launch still covers the 256 CUs
+  {
+    const long long big_tiles = (long long)cdiv(k.OHW, 128) * cdiv(d->Cout, 128) * d->B;
+    if (d->Cout > 32 && big_tiles < 192) {
+      // stages follow the K depth: a stage is 16 KB of LDS, and with one or two K-slabs occupancy (workgroups whose
+      // prologue / epilogue latencies overlap) is worth more than prefetch depth
+      const int nK = cdiv(k.Ktot, BK);
+      if (nK <= 2) return ROUTE_S64_NST2;
+      if (nK <= 4) return ROUTE_S64_NST3;
+      // deep K on a grid that cannot even cover the CUs (the spatial-reduction convs: 32 workgroups x 32..64 K-slabs)
+      const long long small_tiles = (long long)cdiv(k.OHW, 64) * cdiv(d->Cout, 64) * d->B;
+      if (nK >= 8 && small_tiles <= 256) return ROUTE_S64_SPLITK4;   // 4-way split-K inside the workgroup (2 x 4 stages measured slower)
+      return ROUTE_S64_NST4;
+    }
+  }
+  if (d->Cout <= 32) return ROUTE_T128x32;
+  if (d->Cout <= 64) return ROUTE_T128x64;
+  if (d->Cout <= 96) return ROUTE_T128x96;
+  if (d->Cout > 128 && d->Cout <= 160) return ROUTE_T128x160;
+  return ROUTE_T128x128;
+}
+
+// The argument checks of crd_conv_igemm and the argument block of a descriptor that passes them (shared with crd_conv_igemm_route:
+// same status, same message).
+int igemm_args(const crd_conv_desc* d, ConvK& k, long long& pcap) {
   CRD_CHECK_ARG(d && d->x && d->w && d->y, "crd_conv_igemm: null pointer");
   CRD_CHECK_ARG(d->Cin % 8 == 0 && d->x_ld % 8 == 0 && d->x_coff % 8 == 0,
                 "crd_conv_igemm: Cin/x_ld/x_coff must be multiples of 8 (got %d/%d/%d)", d->Cin, d->x_ld, d->x_coff);
@@ -300,11 +393,9 @@ extern "C" int crd_conv_igemm(const crd_conv_desc* d, crd_stream_t stream) {
                   "crd_conv_igemm: image or weight tensor too large for 32-bit byte offsets");
   CRD_UNSUPPORTED(!d->chan_sums || (d->stats && (d->y_f32 || d->res || d->out_mode != 0)),
                   "crd_conv_igemm: chan_sums needs stats and an fp32 / residual output (the scalar epilogue)");
-  ConvK k;
   convk_from_desc(*d, k);
   k.stats_partial = d->stats ? d->stats_partial : nullptr;       // per-tile partial sums only where there are sums
-  const long long pcap = d->stats_partial ? d->stats_partial_capacity : 0;
-  hipStream_t st = as_stream(stream);
+  pcap = d->stats_partial ? d->stats_partial_capacity : 0;
   if (d->red_x) {
     const bool halo_shape = d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->IW >= 32 && d->IH >= 8;
     CRD_CHECK_ARG(d->red_stats && d->red_gamma && d->red_beta && d->red_r && d->red_gmul >= 1 && d->red_x_ld % 8 == 0 &&
@@ -316,47 +407,50 @@ extern "C" int crd_conv_igemm(const crd_conv_desc* d, crd_stream_t stream) {
     CRD_UNSUPPORTED(tile_ok && d->Cout % 16 == 0 && !halo_shape && d->out_mode == 0 && !d->y_f32 && !d->res && d->y_ld % 8 == 0 &&
                     k.vec_ok, "crd_conv_igemm: the fused GroupNorm-backward reduce needs a bf16 vector-path output and a 32/64/128-column tile");
   }
-  // 3x3 / stride 1 / pad 1 on grids at least one tile wide: halo-tile kernel (conv3x3.hip)
-  if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->out_mode == 0 && d->IH == d->OH && d->IW == d->OW &&
-      d->IW >= 32 && d->IH >= 8)
-    return crd_conv3x3_halo(k, d->B, st, pcap);
-  // pointwise layers that are all INPUT (Mlp.fc2 and fc1's data gradient at encoder stages 1-2): weights in registers, rows streamed once
-  if (d->KH == 1 && d->KW == 1 && crd_pw_narrow_applicable(k, nullptr)) return crd_pw_narrow(k, nullptr, d->B, st);
-  // pointwise layers that are all output (fc2's data gradient at encoder stages 1-2): the register-resident-weight kernel
-  if (d->KH == 1 && d->KW == 1 && crd_pw_wide_plain_applicable(k)) return crd_pw_wide_plain(k, d->B, st);
-  {   // developer override of the tile choice below (tools/bench_small_gemm.py sweeps it)
-    static int force = -1;
-    if (force < 0) force = crd_dev_int("CRD_IGEMM_FORCE", 0);
-    switch (force) {
-      case 1: return launch<2, 2, 1, 1, 4>(k, d->B, st, pcap);
-      case 2: return launch<2, 2, 2, 1, 3>(k, d->B, st, pcap);
-      case 3: return launch<2, 2, 2, 2, 2>(k, d->B, st, pcap);
-      case 4: return launch<2, 2, 1, 1, 2, 4>(k, d->B, st, pcap);
-      case 5: return launch<2, 2, 1, 1, 3>(k, d->B, st, pcap);
-      case 6: return launch<2, 2, 1, 1, 2>(k, d->B, st, pcap);
-      default: break;
-    }
+  return CRD_OK;
+}
+
+}  // namespace
+
+extern "C" int crd_conv_igemm_route(const crd_conv_desc* d, char* label, int32_t capacity) {
+  ConvK k;
+  long long pcap;
+  const int rc = igemm_args(d, k, pcap);
+  if (rc != CRD_OK) return rc;
+  CRD_CHECK_ARG(label && capacity > 0, "crd_conv_igemm_route: no room for a label (capacity %d)", capacity);
+  label[0] = 0;
+  const char* family = nullptr;
+  switch (igemm_route(d, k)) {
+    case ROUTE_HALO3X3: family = crd_conv3x3_halo_persistent(k, d->B, pcap) ? "conv3x3p" : "conv3x3_halo"; break;
+    case ROUTE_PW_NARROW: family = "pw_narrow"; break;
+    case ROUTE_PW_WIDE_PLAIN: family = "pw_wide_plain"; break;
+#define X(name, WM, WN, TM, TN, NST, KG) \
+    case ROUTE_##name: return describe<WM, WN, TM, TN, NST, KG>(k, d->B, pcap, label, capacity);
+    CRD_IGEMM_TILES(X)
+#undef X
   }
-  // small problems: 64x64 tiles so that the launch still covers the 256 CUs
-  {
-    const long long big_tiles = (long long)cdiv(k.OHW, 128) * cdiv(d->Cout, 128) * d->B;
-    if (d->Cout > 32 && big_tiles < 192) {
-      // stages follow the K depth: a stage is 16 KB of LDS, and with one or two K-slabs occupancy (workgroups whose
-      // prologue / epilogue latencies overlap) is worth more than prefetch depth
-      const int nK = cdiv(k.Ktot, BK);
-      if (nK <= 2) return launch<2, 2, 1, 1, 2>(k, d->B, st, pcap);
-      if (nK <= 4) return launch<2, 2, 1, 1, 3>(k, d->B, st, pcap);
-      // deep K on a grid that cannot even cover the CUs (the spatial-reduction convs: 32 workgroups x 32..64 K-slabs)
-      const long long small_tiles = (long long)cdiv(k.OHW, 64) * cdiv(d->Cout, 64) * d->B;
-      if (nK >= 8 && small_tiles <= 256) return launch<2, 2, 1, 1, 2, 4>(k, d->B, st, pcap);   // 4-way split-K inside the workgroup (2 x 4 stages measured slower)
-      return launch<2, 2, 1, 1, 4>(k, d->B, st, pcap);
-    }
+  const int n = snprintf(label, capacity, "%s", family);
+  CRD_CHECK_ARG(n < capacity, "crd_conv_igemm_route: the label needs %d bytes, capacity is %d", n + 1, capacity);
+  return CRD_OK;
+}
+
+extern "C" int crd_conv_igemm(const crd_conv_desc* d, crd_stream_t stream) {
+  ConvK k;
+  long long pcap;
+  const int rc = igemm_args(d, k, pcap);
+  if (rc != CRD_OK) return rc;
+  hipStream_t st = as_stream(stream);
+  switch (igemm_route(d, k)) {
+    case ROUTE_HALO3X3: return crd_conv3x3_halo(k, d->B, st, pcap);
+    case ROUTE_PW_NARROW: return crd_pw_narrow(k, nullptr, d->B, st);
+    case ROUTE_PW_WIDE_PLAIN: return crd_pw_wide_plain(k, d->B, st);
+#define X(name, WM, WN, TM, TN, NST, KG) \
+    case ROUTE_##name: return launch<WM, WN, TM, TN, NST, KG>(k, d->B, st, pcap);
+    CRD_IGEMM_TILES(X)
+#undef X
   }
-  if (d->Cout <= 32) return launch<4, 1, 1, 1, 3>(k, d->B, st, pcap);
-  if (d->Cout <= 64) return launch<2, 2, 2, 1, 3>(k, d->B, st, pcap);
-  if (d->Cout <= 96) return launch<4, 1, 1, 3, 2>(k, d->B, st, pcap);
-  if (d->Cout > 128 && d->Cout <= 160) return launch<4, 1, 1, 5, 2>(k, d->B, st, pcap);
-  return launch<2, 2, 2, 2, 2>(k, d->B, st, pcap);
+  crd_set_error("crd_conv_igemm: no route");
+  return CRD_E_INVALID;
 }
 
 extern "C" int crd_tune_igemm_reg_epilogue(int32_t on) {

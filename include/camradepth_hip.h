@@ -120,6 +120,18 @@ typedef struct {
 } crd_conv_desc;
 
 int crd_conv_igemm(const crd_conv_desc* d, crd_stream_t stream);
+/* Which kernel crd_conv_igemm(d) would launch right now, as a NUL-terminated label (host arithmetic only: nothing is launched, no
+ * device memory is read, no launch counter moves).  Runs the argument checks of crd_conv_igemm first: same status, same
+ * crd_last_error(); a label that does not fit `capacity` bytes is CRD_E_INVALID.  The launch and this query share one decision
+ * function and the kernels' own epilogue-branch conditions, and the crd_tune_* switches apply to both.
+ *   hand-offs to another kernel family:  "conv3x3_halo", "conv3x3p", "pw_narrow", "pw_wide_plain" (their tile choice is not named)
+ *   the generic kernel:  "k_igemm<WM,WN,TM,TN,MODE=m,NST=n,KG=g>/<epilogue>[+partials|+atomics]"
+ *     tile = 32 WM TM rows x 32 WN TN columns; MODE 0 forward gather, 1 data gradient of a stride-1 layer, 2 strided data gradient;
+ *     NST LDS stages; KG > 1 split-K groups inside the workgroup; epilogue = rege (register epilogue), vec (bf16, 16-byte stores
+ *     through LDS), vecf (fp32 through LDS) or scalar (per lane); with d->stats, how the GroupNorm sums leave the workgroups:
+ *     per-tile partial rows + a finalize launch, or atomics (also when stats_partial_capacity is too small for the chosen tile).
+ * The tests pin the route of every case they mean to run through this (tests/test_conv_routes_cpu.py). */
+int crd_conv_igemm_route(const crd_conv_desc* d, char* label, int32_t capacity);
 
 /* The same convolution with a GroupNorm (+ exact GELU) applied to its INPUT while the A operand is loaded:
  *   y = epilogue( W * act( GroupNorm(x) ) ),   GroupNorm(x)[b,p,c] = (x - mean[b,g]) * rstd[b,g] * gamma[c] + beta[c]

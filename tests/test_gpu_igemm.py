@@ -76,8 +76,10 @@ def run_conv(xpm, x_ld, x_coff, B, IH, IW, Cin, wp, Cout, KH, KW, stride, pad, O
         d.red_x, d.red_x_ld, d.red_gmul, d.red_act = rx.data_ptr(), rx.shape[-1], rgmul, ract
         d.red_x_f32 = 1 if rx.dtype == torch.float32 else 0
         d.red_stats, d.red_gamma, d.red_beta, d.red_r = rstats.data_ptr(), rgamma.data_ptr(), rbeta.data_ptr(), rr.data_ptr()
+    route = lib.conv_route(d)         # the kernel this descriptor launches (crd_conv_igemm_route; tests/test_conv_routes_cpu.py)
     lib.check(L.crd_conv_igemm(C.byref(d), lib.stream()), "crd_conv_igemm")
     torch.cuda.synchronize()
+    return route
 
 
 def assert_close(got, ref, what, rel=4e-3, elem=1e-2):
@@ -258,6 +260,15 @@ def test_conv_dgrad_gather_mode(case):
     assert_close(dx.float().cpu().permute(0, 3, 1, 2), x.grad, f"dgrad {case}")
 
 
+# the kernel behind each fused-reduce case below: 64 x 64 tiles with the register epilogue, their split-K variant (staged vector
+# epilogue), the 128 x 128 tiles at 64 x 104 pixels, and the narrow streaming kernel
+_S64 = "k_igemm<2,2,1,1,MODE=1,"
+FUSED_REDUCE_ROUTE = {(640, 160, 16, 26): _S64 + "NST=3,KG=1>/rege", (512, 64, 24, 40): _S64 + "NST=2,KG=1>/rege", (256, 64, 9, 7): _S64 + "NST=2,KG=1>/rege",
+                      (1024, 256, 2, 3): _S64 + "NST=3,KG=1>/rege", (1024, 256, 8, 13): _S64 + "NST=3,KG=1>/rege",
+                      (1024, 128, 19, 27): _S64 + "NST=2,KG=1>/rege", (512, 64, 64, 104): "k_igemm<2,2,2,2,MODE=1,NST=2,KG=1>/vec",
+                      (160, 640, 16, 26): _S64 + "NST=2,KG=4>/vec", (128, 1024, 32, 52): _S64 + "NST=2,KG=4>/vec", (64, 512, 64, 104): "pw_narrow"}
+
+
 @pytest.mark.parametrize("Ci,Co,H,W,gmul,act,xf32", [(640, 160, 16, 26, 4, 1, 0), (512, 64, 24, 40, 8, 1, 0), (256, 64, 9, 7, 1, 0, 0),
                                                       (1024, 256, 2, 3, 4, 1, 0), (1024, 256, 8, 13, 4, 1, 0), (1024, 128, 19, 27, 8, 1, 0), (512, 64, 64, 104, 8, 1, 0),
                                                       # Mlp.fc1's data gradient feeding Block.norm2 (fp32 residual stream, no activation)
@@ -287,7 +298,8 @@ def test_conv_dgrad_with_fused_groupnorm_backward_reduce(Ci, Co, H, W, gmul, act
                                   gam.data_ptr(), bet.data_ptr(), act, None, r_ref.data_ptr(), None, 0, lib.stream()), "gn_bwd_reduce")
     dx1 = torch.zeros_like(dx0)
     r = torch.zeros_like(r_ref)
-    run_conv(dypm, Co, 0, B, H, W, Co, wd, Ci, 1, 1, 1, 0, H, W, dx1, Ci, 0, gather_mode=1, red=(xg, stats, gam, bet, gmul, act, r))
+    route = run_conv(dypm, Co, 0, B, H, W, Co, wd, Ci, 1, 1, 1, 0, H, W, dx1, Ci, 0, gather_mode=1, red=(xg, stats, gam, bet, gmul, act, r))
+    assert route == FUSED_REDUCE_ROUTE[(Ci, Co, H, W)]
     assert torch.equal(dx0, dx1)
     assert_close(gval(r), gval(r_ref), "fused gn-bwd reduce", rel=3e-4, elem=3e-4)
 
@@ -306,7 +318,8 @@ def test_conv_dgrad_patch_scatter(k, C):
     ws = w.permute(2, 3, 1, 0).contiguous().reshape(k * k * C, 1, C).to(torch.bfloat16).cuda()
     dypm = to_pm(dy)
     dx = torch.zeros(B, H, W, C, dtype=torch.bfloat16, device="cuda")
-    run_conv(dypm, C, 0, B, PH, PW, C, ws, k * k * C, 1, 1, 1, 0, PH, PW, dx, C, 0, out_mode=1, patch_k=k, patch_c=C)
+    route = run_conv(dypm, C, 0, B, PH, PW, C, ws, k * k * C, 1, 1, 1, 0, PH, PW, dx, C, 0, out_mode=1, patch_k=k, patch_c=C)
+    assert route == "k_igemm<2,2,1,1,MODE=0,NST=%d,KG=1>/vec" % (3 if C == 160 else 2)        # 64 x 64 tiles at B = 2, 16-byte scatter stores
     assert_close(dx.float().cpu().permute(0, 3, 1, 2), x.grad, f"scatter k={k}")
     # accumulate into an existing bf16 gradient (how the sr path adds into d(XN)) -- the 16-byte read-modify-write epilogue
     base = bf(torch.randn(B, H, W, C, generator=g))
