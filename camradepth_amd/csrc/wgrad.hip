@@ -16,6 +16,7 @@
 
 int crd_wgrad3x3_stream(const crd_wgrad_desc* d, hipStream_t st);   // wgrad3x3.hip
 int crd_wgrad3x3_splits(const crd_wgrad_desc* d);
+int crd_wgrad3x3_route(const crd_wgrad_desc* d, char* label, int capacity);
 
 namespace {
 
@@ -226,20 +227,45 @@ long long plan_splits(WgK& k, int tiles, long long want, int min_steps) {
   return (steps + chunk_steps - 1) / chunk_steps;
 }
 
+// One launch of the generic kernel, decided once: the argument block with its K split (chunk), the grid.  crd_conv_wgrad launches from
+// it and crd_conv_wgrad_route prints it: neither decides anything on its own.
+struct WgLaunch {
+  WgK k;
+  dim3 grid;             // (kf tiles, co tiles, K splits)
+};
+
+template <int WMc, int WNc, int TMc, int TNc>
+WgLaunch prepare(const WgK& k0) {
+  WgLaunch p;
+  p.k = k0;
+  constexpr int BMc = WMc * TMc * 16, BNk = WNc * TNc * 16;
+  const int tn = cdiv(p.k.Ktot, BNk), tm = cdiv(p.k.Cout, BMc);
+  const long long splits = plan_splits(p.k, tn * tm, (1536 + tn * tm - 1) / (tn * tm), 4);   // ~6 workgroups per CU in flight
+  p.grid = dim3(tn, tm, (unsigned)splits);
+  return p;
+}
+
 template <int WMc, int WNc, int TMc, int TNc>
 int launch(const WgK& k0, hipStream_t st) {
-  WgK k = k0;
-  constexpr int BMc = WMc * TMc * 16, BNk = WNc * TNc * 16;
-  const int tn = cdiv(k.Ktot, BNk), tm = cdiv(k.Cout, BMc);
-  const long long splits = plan_splits(k, tn * tm, (1536 + tn * tm - 1) / (tn * tm), 4);   // ~6 workgroups per CU in flight
-  dim3 grid(tn, tm, (unsigned)splits);
-  hipLaunchKernelGGL((k_wgrad<WMc, WNc, TMc, TNc>), grid, dim3(256), 0, st, k);
+  const WgLaunch p = prepare<WMc, WNc, TMc, TNc>(k0);
+  hipLaunchKernelGGL((k_wgrad<WMc, WNc, TMc, TNc>), p.grid, dim3(256), 0, st, p.k);
   CRD_LAUNCH_CHECK("crd_conv_wgrad");
+  return CRD_OK;
+}
+
+// The label of the same launch: the instantiation, the K splits (grid.z) and the pixels per split.
+template <int WMc, int WNc, int TMc, int TNc>
+int describe(const WgK& k0, char* label, int capacity) {
+  const WgLaunch p = prepare<WMc, WNc, TMc, TNc>(k0);
+  const int n = snprintf(label, capacity, "k_wgrad<%d,%d,%d,%d>/splits=%u,chunk=%d", WMc, WNc, TMc, TNc, p.grid.z, p.k.chunk);
+  CRD_CHECK_ARG(n < capacity, "crd_conv_wgrad_route: the label needs %d bytes, capacity is %d", n + 1, capacity);
   return CRD_OK;
 }
 
 int fill(const crd_wgrad_desc* d, WgK& k) {
   CRD_CHECK_ARG(d && d->x && d->dy && d->dw, "crd_conv_wgrad: null pointer");
+  CRD_CHECK_ARG(d->B > 0 && d->IH > 0 && d->IW > 0 && d->Cin > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 &&
+                d->pad >= 0, "crd_conv_wgrad: bad dims");
   CRD_CHECK_ARG(d->Cin % 8 == 0 && d->x_ld % 8 == 0 && d->x_coff % 8 == 0, "crd_conv_wgrad: x channels must be multiples of 8");
   CRD_CHECK_ARG(d->dy_ld % 8 == 0 && d->dy_coff % 8 == 0, "crd_conv_wgrad: dy_ld/dy_coff must be multiples of 8");
   CRD_CHECK_ARG(d->Cout % 8 == 0 || d->dy_ld - d->dy_coff >= ((d->Cout + 7) / 8) * 8,
@@ -258,9 +284,21 @@ int check_generic(const WgK& k) {   // the generic split-K kernel addresses the 
   return CRD_OK;
 }
 
+// What crd_conv_wgrad checks on a problem of the generic kernel beyond fill() (shared with crd_conv_wgrad_route: same status, same message)
+int generic_args(const crd_wgrad_desc* d, const WgK& k) {
+  CRD_CHECK_ARG(d->dw_partials == nullptr, "crd_conv_wgrad: dw_partials is only supported where crd_conv_wgrad_splits() > 0");
+  return check_generic(k);
+}
+
 // tile configuration of the generic kernel by output-channel count (index into the launch tables)
 int cfg_of(int cout) { return cout <= 32 ? 0 : cout <= 64 ? 1 : cout <= 96 ? 2 : 3; }
 const int CFG_BM[4] = {32, 64, 96, 128};
+// Every instantiation of the generic kernel: index (cfg_of), WM, WN, TM, TN.  The launch switch and the label switch of crd_conv_wgrad /
+// crd_conv_wgrad_route are both generated from this list.
+#define CRD_WGRAD_TILES(X) X(0, 1, 4, 2, 2) X(1, 1, 4, 4, 2) X(2, 2, 2, 3, 4) X(3, 2, 2, 4, 4)
+#define X(c, WM, WN, TM, TN) static_assert(WM * TM * 16 == (c + 1) * 32, "CFG_BM");
+CRD_WGRAD_TILES(X)
+#undef X
 
 }  // namespace
 
@@ -353,9 +391,12 @@ extern "C" int crd_conv_wgrad_grouped(const void* dev_table, const crd_wgrad_gro
   return CRD_OK;
 }
 
+// THE routing rule of crd_conv_wgrad, for a descriptor that has passed fill(): 3x3 / stride 1 / pad 1 on grids at least one 32-pixel
+// strip wide and at most 128 output channels go to the streaming halo-row kernel (wgrad3x3.hip).  Its widest instance stages and
+// accumulates 128 output channels per workgroup; wider layers take the generic kernel.
 static bool uses_stream3(const crd_wgrad_desc* d) {
   return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->IH == d->OH && d->IW == d->OW && d->IW >= 32 &&
-         d->IH >= 8 && !crd_dev_int("CRD_NO_WGRAD3", 0);
+         d->IH >= 8 && d->Cout <= 128 && !crd_dev_int("CRD_NO_WGRAD3", 0);
 }
 
 extern "C" int crd_conv_wgrad_splits(const crd_wgrad_desc* d) {
@@ -363,17 +404,34 @@ extern "C" int crd_conv_wgrad_splits(const crd_wgrad_desc* d) {
   return crd_wgrad3x3_splits(d);
 }
 
+extern "C" int crd_conv_wgrad_route(const crd_wgrad_desc* d, char* label, int32_t capacity) {
+  WgK k;
+  { int rc = fill(d, k); if (rc != CRD_OK) return rc; }
+  CRD_CHECK_ARG(label && capacity > 0, "crd_conv_wgrad_route: no room for a label (capacity %d)", capacity);
+  label[0] = 0;
+  if (uses_stream3(d)) return crd_wgrad3x3_route(d, label, capacity);
+  { int rc = generic_args(d, k); if (rc != CRD_OK) return rc; }
+  switch (cfg_of(d->Cout)) {
+#define X(c, WM, WN, TM, TN) case c: return describe<WM, WN, TM, TN>(k, label, capacity);
+    CRD_WGRAD_TILES(X)
+#undef X
+  }
+  crd_set_error("crd_conv_wgrad_route: no route");
+  return CRD_E_INVALID;
+}
+
 extern "C" int crd_conv_wgrad(const crd_wgrad_desc* d, crd_stream_t stream) {
   WgK k;
   { int rc = fill(d, k); if (rc != CRD_OK) return rc; }
   hipStream_t st = as_stream(stream);
-  // 3x3 / stride 1 / pad 1 on grids at least one 32-pixel strip wide: streaming halo-row kernel (wgrad3x3.hip)
   if (uses_stream3(d)) return crd_wgrad3x3_stream(d, st);
-  CRD_CHECK_ARG(d->dw_partials == nullptr, "crd_conv_wgrad: dw_partials is only supported where crd_conv_wgrad_splits() > 0");
-  { int rc = check_generic(k); if (rc != CRD_OK) return rc; }
+  { int rc = generic_args(d, k); if (rc != CRD_OK) return rc; }
   { static int dbg = -1; if (dbg < 0) dbg = crd_dev_int("CRD_DBG", 0); k.dbg = dbg; }
-  if (d->Cout <= 32) return launch<1, 4, 2, 2>(k, st);
-  if (d->Cout <= 64) return launch<1, 4, 4, 2>(k, st);
-  if (d->Cout <= 96) return launch<2, 2, 3, 4>(k, st);
-  return launch<2, 2, 4, 4>(k, st);
+  switch (cfg_of(d->Cout)) {
+#define X(c, WM, WN, TM, TN) case c: return launch<WM, WN, TM, TN>(k, st);
+    CRD_WGRAD_TILES(X)
+#undef X
+  }
+  crd_set_error("crd_conv_wgrad: no route");
+  return CRD_E_INVALID;
 }

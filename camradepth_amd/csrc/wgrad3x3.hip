@@ -258,13 +258,28 @@ int plan_rows(long long total_rows, int Cin, int& rows_per_wg, int budget, int c
   return (int)((total_rows + rows_per_wg - 1) / rows_per_wg);
 }
 
+// One launch, decided once: the argument block with its row splits, the LDS it needs.  crd_wgrad3x3_stream launches from it and
+// crd_wgrad3x3_route prints it.
 template <int WCO, int WCI, int TCO, int RPS>
-int launch_w3r(const Wg3K& k0, hipStream_t st, int budget, int partial_capacity) {
+Wg3K prepare_w3r(const Wg3K& k0, int budget, int partial_capacity, size_t& lds) {
   Wg3K k = k0;
   constexpr int COT = WCO * TCO * 16;
-  const size_t lds = (size_t)RPS * (XS * XPX * XLD + YS * 32 * COT) * sizeof(bf16_t);
+  lds = (size_t)RPS * (XS * XPX * XLD + YS * 32 * COT) * sizeof(bf16_t);
   k.nchunks = cdiv(k.Cin, XLD);
   k.S = plan_rows(k.total_rows, k.Cin, k.rows_per_wg, budget, k.dw_part ? partial_capacity : 0);
+  return k;
+}
+
+// label == nullptr: launch; otherwise write the label of that launch
+template <int WCO, int WCI, int TCO, int RPS>
+int launch_w3r(const Wg3K& k0, hipStream_t st, int budget, int partial_capacity, char* label, int capacity) {
+  size_t lds;
+  const Wg3K k = prepare_w3r<WCO, WCI, TCO, RPS>(k0, budget, partial_capacity, lds);
+  if (label) {
+    const int n = snprintf(label, capacity, "k_wgrad3x3<%d,%d,%d,%d>/S=%d,rows_per_wg=%d,chunks=%d", WCO, WCI, TCO, RPS, k.S, k.rows_per_wg, k.nchunks);
+    CRD_CHECK_ARG(n < capacity, "crd_conv_wgrad_route: the label needs %d bytes, capacity is %d", n + 1, capacity);
+    return CRD_OK;
+  }
   crd_reserve_lds_once<&k_wgrad3x3<WCO, WCI, TCO, RPS>>((int)lds, "k_wgrad3x3");
   hipLaunchKernelGGL((k_wgrad3x3<WCO, WCI, TCO, RPS>), dim3(k.nchunks * k.S), dim3(512), lds, st, k);
   CRD_LAUNCH_CHECK("crd_conv_wgrad(3x3 streaming)");
@@ -272,16 +287,17 @@ int launch_w3r(const Wg3K& k0, hipStream_t st, int budget, int partial_capacity)
 }
 
 template <int WCO, int WCI, int TCO>
-int launch_w3(const Wg3K& k, hipStream_t st, int budget, int partial_capacity) {
+int launch_w3(const Wg3K& k, hipStream_t st, int budget, int partial_capacity, char* label, int capacity) {
   static int rps = -1;
   if (rps < 0) rps = crd_dev_int("CRD_W3_RPS", 2);
-  return rps == 1 ? launch_w3r<WCO, WCI, TCO, 1>(k, st, budget, partial_capacity) : launch_w3r<WCO, WCI, TCO, 2>(k, st, budget, partial_capacity);
+  return rps == 1 ? launch_w3r<WCO, WCI, TCO, 1>(k, st, budget, partial_capacity, label, capacity)
+                  : launch_w3r<WCO, WCI, TCO, 2>(k, st, budget, partial_capacity, label, capacity);
 }
 
-}  // namespace
-
-// Called from crd_conv_wgrad for 3x3 / stride 1 / pad 1 layers on grids at least one strip wide.
-int crd_wgrad3x3_stream(const crd_wgrad_desc* d, hipStream_t st) {
+// The argument checks, the argument block and the tile choice of the streaming kernel; crd_conv_wgrad reaches it with label == nullptr (launch),
+// crd_conv_wgrad_route with a label to fill (nothing is launched).  Called for 3x3 / stride 1 / pad 1 layers of at most 128 output channels
+// on grids at least one strip wide.
+int w3_dispatch(const crd_wgrad_desc* d, hipStream_t st, char* label, int capacity) {
   Wg3K k;
   k.x = reinterpret_cast<const bf16_t*>(d->x) + d->x_coff; k.x_ld = d->x_ld; k.Cin = d->Cin;
   k.dy = reinterpret_cast<const bf16_t*>(d->dy) + d->dy_coff; k.dy_ld = d->dy_ld; k.Cout = d->Cout;
@@ -296,15 +312,22 @@ int crd_wgrad3x3_stream(const crd_wgrad_desc* d, hipStream_t st) {
   k.dw_part = d->dw_partials;
   CRD_CHECK_ARG(d->dw_partials == nullptr || d->dw_partial_capacity >= 1, "crd_conv_wgrad: dw_partials needs a capacity >= 1");
   CRD_CHECK_ARG(d->wg_budget >= 0, "crd_conv_wgrad: wg_budget must be >= 0");
-  if (d->Cout <= 32) return launch_w3<2, 4, 1>(k, st, d->wg_budget, d->dw_partial_capacity);
-  if (d->Cout <= 64) return launch_w3<2, 4, 2>(k, st, d->wg_budget, d->dw_partial_capacity);
-  if (d->Cout <= 96) return launch_w3<2, 4, 3>(k, st, d->wg_budget, d->dw_partial_capacity);     // 96-channel dy rows: no padded MFMA tiles
+  // the widest instance stages COT = 128 channels of dy per row: rows co >= 128 would never be accumulated or written (wgrad.hip: uses_stream3)
+  CRD_UNSUPPORTED(d->Cout <= 128, "crd_conv_wgrad: the streaming 3x3 kernel covers at most 128 output channels");
+  if (d->Cout <= 32) return launch_w3<2, 4, 1>(k, st, d->wg_budget, d->dw_partial_capacity, label, capacity);
+  if (d->Cout <= 64) return launch_w3<2, 4, 2>(k, st, d->wg_budget, d->dw_partial_capacity, label, capacity);
+  if (d->Cout <= 96) return launch_w3<2, 4, 3>(k, st, d->wg_budget, d->dw_partial_capacity, label, capacity);     // 96-channel dy rows: no padded MFMA tiles
   // 128 output channels: FOUR co tiles x one ci tile per wave.  Per strip row a wave then reads 8 dy + 18 input fragments for its 36
   // MFMAs; with 2 x 2 tiles (round 2-3) it was 4 + 36 -- the kernel is bound by those LDS reads (0.716 -> 0.658 ms at 304 -> 128,
   // 0.293 -> 0.262 ms at 128 -> 128, 256 x 416 x 8)
-  if (crd_dev_int("CRD_W3_T22", 0)) return launch_w3<4, 2, 2>(k, st, d->wg_budget, d->dw_partial_capacity);
-  return launch_w3<2, 4, 4>(k, st, d->wg_budget, d->dw_partial_capacity);
+  if (crd_dev_int("CRD_W3_T22", 0)) return launch_w3<4, 2, 2>(k, st, d->wg_budget, d->dw_partial_capacity, label, capacity);
+  return launch_w3<2, 4, 4>(k, st, d->wg_budget, d->dw_partial_capacity, label, capacity);
 }
+
+}  // namespace
+
+int crd_wgrad3x3_stream(const crd_wgrad_desc* d, hipStream_t st) { return w3_dispatch(d, st, nullptr, 0); }
+int crd_wgrad3x3_route(const crd_wgrad_desc* d, char* label, int capacity) { return w3_dispatch(d, nullptr, label, capacity); }
 
 int crd_wgrad3x3_splits(const crd_wgrad_desc* d) {
   int rows = 0;

@@ -322,7 +322,8 @@ class Plan:
             dbias = rows
         spec = dict(kind="wg", x=x, dy=dy, cw=cw, k=k, stride=stride, pad=pad, OH=OH, OW=OW, dbias=dbias,
                     cin=cin if cin is not None else x.C)
-        stream3 = k == 3 and stride == 1 and OW >= 32 and OH >= 8
+        # the streaming kernel's layers (3x3 / stride 1 / pad 1, OW >= 32, OH >= 8, at most 128 output channels): the library's own rule
+        stream3 = k == 3 and tables.stream3_splits(self.lib, self.B, x.H, x.W, spec["cin"], cw.cout, k, stride, pad) > 0
         if stream3:
             cw.stream3_geom = (x.H, x.W, spec["cin"])
         meta = {"kernel": wgrad3_tile(cw.cout) if stream3 else wgrad_tile(cw.cout), "flops": 2.0 * self.B * OH * OW * cw.cout * cw.cin_ref * cw.taps, "param": cw.name,

@@ -138,7 +138,7 @@ def load():
 _SIGS = {
     "crd_conv_igemm": "pp", "crd_conv_igemm_route": "ppi", "crd_gn_conv": "ppp", "crd_gn_conv2": "ppppp", "crd_gn_bwd_conv": "ppp", "crd_pw_narrow_supported": "iii", "crd_tune_pw_narrow": "i", "crd_conv3x3_fp8": "ppfp", "crd_amax_bf16": "pliiipp", "crd_quant_fp8": "pliiipiifp",
     "crd_weight_quant_fp8": "piiiippp", "crd_conv3x3_fp8_dgrad": "pppp", "crd_gn_bwd_apply_fp8": "piiipiiiiiipippipppppiipiippp",
-    "crd_fp8_scale_update": "ppifip", "crd_quant_fp8_dev": "pliiipiipp", "crd_tune_conv3x3_small_grid": "i", "crd_tune_igemm_reg_epilogue": "i", "crd_conv_wgrad": "pp", "crd_conv_wgrad_splits": "p", "crd_wgrad_group_build": "piplp", "crd_conv_wgrad_grouped": "ppp",
+    "crd_fp8_scale_update": "ppifip", "crd_quant_fp8_dev": "pliiipiipp", "crd_tune_conv3x3_small_grid": "i", "crd_tune_igemm_reg_epilogue": "i", "crd_conv_wgrad": "pp", "crd_conv_wgrad_splits": "p", "crd_conv_wgrad_route": "ppi", "crd_wgrad_group_build": "piplp", "crd_conv_wgrad_grouped": "ppp",
     "crd_gn_stats": "piiiiiippp", "crd_gn_apply": "piiiiiipippipPiiip".replace("P", "p"),
     "crd_gn_bwd_reduce": "piiipiiiiiipippippplp", "crd_gn_bwd_apply": "piiipiiiiiipippipppppiiiipipp",
     "crd_dwconv3x3": "piiiippipppippppppp", "crd_dwconv3x3_wgrad": "ppiiiipipippp",
@@ -238,6 +238,13 @@ def conv_route(desc):
     """Label of the kernel crd_conv_igemm would launch for this ConvDesc right now (crd_conv_igemm_route: host arithmetic, no GPU)."""
     buf = C.create_string_buffer(96)
     check(load().crd_conv_igemm_route(C.byref(desc), buf, len(buf)), "crd_conv_igemm_route")
+    return buf.value.decode()
+
+
+def wgrad_route(desc):
+    """Label of the kernel crd_conv_wgrad would launch for this WgradDesc right now (crd_conv_wgrad_route: host arithmetic, no GPU)."""
+    buf = C.create_string_buffer(96)
+    check(load().crd_conv_wgrad_route(C.byref(desc), buf, len(buf)), "crd_conv_wgrad_route")
     return buf.value.decode()
 
 

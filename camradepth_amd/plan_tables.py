@@ -75,6 +75,17 @@ def build_pack_table(plan):
     plan.n_pack = len(entries)
 
 
+def stream3_splits(lib, B, ih, iw, cin, cout, k=3, stride=1, pad=1, wg_budget=0):
+    """crd_conv_wgrad_splits of a same-size k x k layer: the row splits of the streaming 3x3 weight-gradient kernel, 0 where
+    crd_conv_wgrad sends the layer to the generic kernel.  The routing rule lives in the library (csrc/wgrad.hip: uses_stream3) and is
+    asked, not repeated: the query reads no pointer."""
+    probe = L.WgradDesc()
+    probe.B, probe.IH, probe.IW, probe.OH, probe.OW = B, ih, iw, (ih + 2 * pad - k) // stride + 1, (iw + 2 * pad - k) // stride + 1
+    probe.Cin, probe.Cout, probe.KH, probe.KW, probe.stride, probe.pad = cin, cout, k, k, stride, pad
+    probe.wg_budget = wg_budget
+    return int(lib.crd_conv_wgrad_splits(C.byref(probe)))
+
+
 def place_weight_gradients(plan):
     """-> cw.dw (+ dw_parts, dw_S, wg_budget) of every trainable convolution; returns those convolutions.
     Destination: a crd_sum_t scratch block (order-independent integer atomics) that the segment's unpack converts.  The streaming
@@ -86,12 +97,8 @@ def place_weight_gradients(plan):
             continue
         if cw.stream3_geom is not None:
             ih, iw, cin = cw.stream3_geom
-            probe = L.WgradDesc()
-            probe.B, probe.IH, probe.IW, probe.OH, probe.OW = plan.B, ih, iw, ih, iw
-            probe.Cin, probe.Cout, probe.KH, probe.KW, probe.stride, probe.pad = cin, cw.cout, 3, 3, 1, 1
             cw.wg_budget = int(getattr(plan.model, "w3_total_wgs", None) or 0)      # set by TrainStep in late-wgrad mode
-            probe.wg_budget = cw.wg_budget
-            cw.dw_S = int(plan.lib.crd_conv_wgrad_splits(C.byref(probe)))
+            cw.dw_S = stream3_splits(plan.lib, plan.B, ih, iw, cin, cw.cout, wg_budget=cw.wg_budget)
         if cw.dw_S > 0:
             cw.dw = cw.dw_parts = plan.new((cw.dw_S, cw.cout, cw.taps, cw.cin_pad), F32)
         else:

@@ -280,10 +280,26 @@ typedef struct {
                                     workgroups and more rows each */
 } crd_wgrad_desc;
 
+/* Two kernel families serve this entry.  3x3 / stride 1 / pad 1 layers on grids of IW >= 32, IH >= 8 with Cout <= 128 go to the
+ * streaming halo-row kernel (its widest instance stages and accumulates 128 output channels per workgroup: that is the limit);
+ * everything else -- wider 3x3 layers included -- goes to the generic split-K kernel, which has no Cout limit but addresses the whole
+ * batch with 32-bit byte offsets (CRD_E_UNSUPPORTED beyond).  Cin, x_ld, x_coff, dy_ld and dy_coff are multiples of 8; a dy row holds
+ * Cout rounded up to 8 channels from dy_coff on (the channels of that round-up may hold anything: they are read, never stored). */
 int crd_conv_wgrad(const crd_wgrad_desc* d, crd_stream_t stream);
 /* Number of pixel-range splits the 3x3 streaming kernel uses for this problem (honouring d->dw_partial_capacity > 0 as
- * a cap), 0 if the generic kernel handles it. */
+ * a cap), 0 if the generic kernel handles it (every layer of more than 128 output channels among them). */
 int crd_conv_wgrad_splits(const crd_wgrad_desc* d);
+/* Which kernel crd_conv_wgrad(d) would launch right now, as a NUL-terminated label (host arithmetic only: nothing is launched, no
+ * device memory is read).  Runs the argument checks of crd_conv_wgrad first: same status, same crd_last_error(); a label that does
+ * not fit `capacity` bytes is CRD_E_INVALID.  The launch and this query share the routing rule, the tile choice and the split planning.
+ *   the generic kernel:    "k_wgrad<WM,WN,TM,TN>/splits=s,chunk=c"
+ *     tile = 16 WM TM output channels x 128 (tap, ci) columns; s pixel-range splits (grid.z) of c pixels each, the last one shorter
+ *   the streaming kernel:  "k_wgrad3x3<WCO,WCI,TCO,RPS>/S=s,rows_per_wg=r,chunks=n"
+ *     16 WCO TCO output channels staged per row, RPS image rows per step; n 64-channel chunks of Cin x s row splits = workgroups,
+ *     each split walking r consecutive strip rows (a strip = 32 columns of one image, B ceil(IW/32) IH strip rows in all).
+ *     s is what crd_conv_wgrad_splits returns when dw_partials is given; d->dw_partial_capacity caps it only together with dw_partials.
+ * A new entry, no changed signature: CRD_ABI_VERSION stays.  tests/test_wgrad_routes_cpu.py pins the route of every case it means to run. */
+int crd_conv_wgrad_route(const crd_wgrad_desc* d, char* label, int32_t capacity);
 
 /* Grouped weight gradients: the ~190 small wgrads of the encoder blocks (autograd's per-layer conv2d_backward weight
  * calls behind simplified_attention.py:32-43,95-132) are each too small to fill the chip, so the host collects them

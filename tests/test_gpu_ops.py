@@ -325,13 +325,14 @@ def test_dwconv(C_, H, W):
         assert_close(tot[9], b.grad, "dwconv db", rel=2e-3, elem=4e-3)
 
 
-@pytest.mark.parametrize("C_,H,W,gmul", [(64, 9, 13, 1), (256, 17, 40, 4), (80, 8, 33, 1)])
+@pytest.mark.parametrize("C_,H,W,gmul", [(64, 9, 13, 1), (256, 17, 40, 4), (80, 8, 33, 1), (1024, 66, 20, 4)])
 def test_dwconv_with_fused_input_groupnorm(C_, H, W, gmul):
     """in_stats != NULL: GroupNorm of the input applied while the halo is staged == crd_gn_apply followed by the plain
-    kernel, bit for bit (forward, statistics and weight gradient)."""
+    kernel, bit for bit (forward, statistics and weight gradient).  The last shape (B = 4) puts the weight gradient on runs of two
+    tiles per workgroup with a one-tile last run (tests/test_wgrad_routes_cpu.py: dw_plan)."""
     lib, lb = L()
     g = torch.Generator().manual_seed(8)
-    B = 2
+    B = 4 if (C_, H, W) == (1024, 66, 20) else 2
     if (C_ // 16) % gmul:
         gmul = 1
     xd = to_pm(bf(torch.randn(B, C_, H, W, generator=g) * 2 + 0.5))
