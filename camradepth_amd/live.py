@@ -1,6 +1,6 @@
 """Raw sensors to depth, point cloud and pictures in ONE captured graph: the camera front end, the radar front end, the input
-assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid and the occupancy map behind it, if asked
-for) and the visualiser on static buffers, replayed once per frame.
+assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid, the occupancy map and its distance field
+behind it, if asked for) and the visualiser on static buffers, replayed once per frame.
 
 Each stage exists on its own (camera.camera_inputs, radar.radar_inputs, batch.assemble_batch, inference.InferenceGraph,
 cloud.point_cloud, viz.Visualizer) and LivePipeline.run returns the bits of calling them one by one; what it adds is the ownership of
@@ -10,6 +10,7 @@ import math
 
 import torch
 
+from . import field as fld
 from . import lib as L
 from . import occupancy as occ
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
@@ -24,6 +25,9 @@ BEV_OPTIONS = dict(GRID_OPTIONS, picture=False, picture_z_range=(-2.0, 4.0), cma
 # the map's own options (OccupancyMap), M (None: one map per frame; 1: the frames are the cameras of one rig), centre (None: the
 # camera; or a point of the out frame the window is centred on, such as (20, 0, 0)) and picture (True: also occupancy.picture in cmap)
 OCCUPANCY_OPTIONS = dict(occ.MAP_OPTIONS, nx=160, ny=160, cell=0.5, M=None, centre=None, picture=False, cmap="jet")
+# the FieldSpec's own options (its cell is the map's), picture (True: also field.picture in cmap), paths ((K, P): also check_paths on K
+# trajectories of P poses that run(paths=) brings) with blocked_at and outside_blocks
+FIELD_OPTIONS = dict(fld.SPEC_OPTIONS, picture=False, cmap="jet", paths=None, blocked_at=253, outside_blocks=True)
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -52,16 +56,26 @@ class LivePipeline:
     occupancy: None, or a dictionary of OCCUPANCY_OPTIONS: an OccupancyMap (`occupancy_map`, owned by this object) fused over the runs,
     fed from the cloud with the pose run(map_from_out=) brings.  It needs cloud=; the camera's position in the cloud's frame is the
     sensor.  The map is empty after construction; occupancy_map.reset() empties it again.
+    field: None, or a dictionary of FIELD_OPTIONS: the distance field of the occupancy map's `state` (field.distance_field), with
+    picture and paths=(K, P) also field.picture and field.check_paths.  It needs occupancy=, whose cell it takes.  The trajectories
+    live in `paths_xy`, fp64 [K,P,2] (all NaN after construction: every pose outside), which run(paths=) fills; `path_n_poses` and
+    `path_map`, int32 [K] (all P poses, map 0), are the caller's to change in place.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture], Visualizer.render."""
+    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture], field.distance_field [, field.picture] [,
+    field.check_paths], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None):
+                 bev=None, occupancy=None, field=None):
         fn = "LivePipeline"
+        if field is not None:
+            if occupancy is None:
+                raise L.CrdError(f"{fn}: field= needs occupancy= (the field is made from the map's state, with its cell)")
+            if not isinstance(field, dict) or not set(field) <= set(FIELD_OPTIONS):
+                raise L.CrdError(f"{fn}: field= holds {sorted(FIELD_OPTIONS)}, not {field!r}")
         if occupancy is not None:
             if cloud is None:
                 raise L.CrdError(f"{fn}: occupancy= needs cloud= (the map is fed from the point cloud)")
@@ -143,6 +157,25 @@ class LivePipeline:
             self.centre = None if centre is None else torch.tensor(centre, dtype=torch.float64, device=dev)
             M = self.occupancy_map.M
             self.occupancy_picture = torch.empty(M, o["nx"], o["ny"], 3, dtype=torch.uint8, device=dev) if o["picture"] else None
+        self.field_opts = None if field is None else dict(FIELD_OPTIONS, **field)
+        self.field_spec = None
+        if self.field_opts is not None:
+            o, omap = self.field_opts, self.occupancy_map
+            self.field_spec = fld.FieldSpec(omap.cell, device=dev, **{k: o[k] for k in fld.SPEC_OPTIONS})
+            self.field_ws = fld.FieldWorkspace(self.field_spec, omap.M, omap.nx, omap.ny)
+            self.field_picture = torch.empty(omap.M, omap.nx, omap.ny, 3, dtype=torch.uint8, device=dev) if o["picture"] else None
+            self.paths_xy = None
+            if o["paths"] is not None:
+                try:
+                    K, P = (int(v) for v in o["paths"])
+                except (TypeError, ValueError):
+                    K = P = 0
+                if K < 1 or P < 1:
+                    raise L.CrdError(f"{fn}: field paths {o['paths']!r} is (K, P), paths and poses per path, each at least 1")
+                self.paths_xy = torch.full((K, P, 2), math.nan, dtype=torch.float64, device=dev)
+                self.path_n_poses = torch.full((K,), P, dtype=torch.int32, device=dev)
+                self.path_map = torch.zeros(K, dtype=torch.int32, device=dev)
+                self.paths_out = fld.path_outputs(K, P, device=dev)
         self.visualizer = None if viz is None else Visualizer(B, h, w, **dict({"image_order": order_out, "device": dev}, **viz))
         # the eval plan, exactly as InferenceGraph takes it
         was_training = model.training
@@ -211,6 +244,16 @@ class LivePipeline:
                 out["occupancy"] = dict(res)
                 if self.occupancy_picture is not None:
                     out["occupancy"]["picture"] = occ.picture(res, self.occupancy_map, self.occupancy_opts["cmap"], out=self.occupancy_picture)
+                if self.field_spec is not None:
+                    o = self.field_opts
+                    dist = fld.distance_field(self.field_spec, res, workspace=self.field_ws, out=self.field_ws.out)
+                    out["field"] = dict(dist)
+                    if self.field_picture is not None:
+                        out["field"]["picture"] = fld.picture(dist, self.field_spec, o["cmap"], out=self.field_picture)
+                    if self.paths_xy is not None:
+                        out["field"]["paths"] = dict(fld.check_paths(self.field_spec, dist, res, self.paths_xy, self.path_n_poses, self.path_map,
+                                                                     blocked_at=o["blocked_at"], outside_blocks=o["outside_blocks"],
+                                                                     out=self.paths_out))
         if self.visualizer is not None:
             out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
         return out
@@ -229,7 +272,7 @@ class LivePipeline:
         dst.copy_(value)
 
     def run(self, frames, points=None, sweep_index=None, frame_offsets=None, cam1_from_sensor=None, cam2_from_sensor=None, lags=None, K=None,
-            out_from_cam=None, clone=False, map_from_out=None):
+            out_from_cam=None, clone=False, map_from_out=None, paths=None):
         """One batch of sensor data through the graph.
 
         frames: uint8 [B,H,W,frame_channels] with any strides (a view of a capture buffer; a host tensor is copied up).  points
@@ -238,11 +281,13 @@ class LivePipeline:
         [3,3] or [B,3,3], the camera's intrinsics at full resolution (the radar projection and the cloud read it; an RGB-only pipeline
         without a cloud needs none).  out_from_cam: fp64 [3,4] or [B,3,4], the cloud's frame; None: the camera's own.  map_from_out:
         fp64 [3,4] or [B,3,4], the pose of the cloud's frame in the occupancy map's frame for this batch (with occupancy= only); None:
-        the identity.
+        the identity.  paths: fp64 [K,P,2], the trajectories of this batch in the map frame (with field=dict(paths=(K, P)) only);
+        None: those of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'occupancy' and 'pictures' (if asked for at construction: the dictionaries of point_cloud,
-        of bev_grid and of occupancy.update -- each with 'picture' if asked for -- and of Visualizer.render).  They are VIEWS of this
+        output dictionary), 'cloud', 'bev', 'occupancy', 'field' and 'pictures' (if asked for at construction: the dictionaries of
+        point_cloud, of bev_grid, of occupancy.update and of field.distance_field -- each with 'picture' if asked for, the last with
+        'paths', check_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call
         does not wait for the device."""
@@ -276,6 +321,10 @@ class LivePipeline:
                            tuple(map_from_out.shape) == (3, 4) else map_from_out, "map_from_out")
         elif map_from_out is not None:
             raise L.CrdError("LivePipeline.run: map_from_out goes with occupancy=")
+        if paths is not None:
+            if self.field_spec is None or self.paths_xy is None:
+                raise L.CrdError("LivePipeline.run: paths goes with field=dict(paths=(K, P))")
+            self._load(self.paths_xy, paths, "paths")
         self.plan.ensure_packed()                   # optimizer step / load_state_dict / mark_params_changed() since the last frame
         self.graph.replay()
         return _copies(self._results) if clone else dict(self._results)

@@ -996,6 +996,58 @@ int crd_occupancy_update(const float* xyz, const uint8_t* valid, const int32_t* 
                          int64_t* origin, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Distance field: a state map -> per cell the squared distance to the nearest source cell, that cell, the clearance in metres and
+ * an inflated costmap; and a check of candidate trajectories against the costmap ("Distance field").  The step after
+ * the occupancy map, with its conventions: no allocation, no synchronisation, capturable in a graph on one stream, arguments checked
+ * before any GPU call, fp64 scalars as IEEE-754 bit patterns.  The two entries add no struct and change no signature:
+ * CRD_ABI_VERSION stays.  The field is integer arithmetic and two table look-ups, the path check adds fp64 divide, floor and compare;
+ * tests/field_ref.py restates both in NumPy and the kernels agree with it bit for bit.
+ *
+ * crd_distance_field, two launches.  state: uint8 [M][nx][ny] in WINDOW order (crd_occupancy_update's `state`, or any uint8 map).
+ * Cell (m, i, j) is a SOURCE when state < 8 and bit `state` of `sources` is set.  R = max_cells, FAR = R * R + 1.  clear_table fp32
+ * [R * R + 2] and cost_table uint8 [R * R + 2] on the device, indexed by a squared distance 0 .. FAR.  Distances do not wrap: the window
+ * is a rectangle here, not the torus.
+ * Launch 1, rows.  row_near[m][i][j] = the j' that is a source of row i with |j - j'| <= R, minimises |j - j'| and is the lower j' of two
+ * equal ones; -1 without one.  row_near, int32 [M][nx][ny], is the workspace.
+ * Launch 2, columns.  The candidates of cell (m, i, j) are the rows i' with 0 <= i' < nx, |i - i'| <= R and j' = row_near[m][i'][j] >= 0;
+ *   t = (i - i') * (i - i') + (j - j') * (j - j')
+ *   dist2     int32   the least t if it is <= R * R, else FAR
+ *   nearest   int32   i' * ny + j' of the winner, the lowest i' among equal t; -1 when FAR
+ *   clearance fp32    clear_table[dist2]                                                              (may be NULL)
+ *   cost      uint8   cost_table[dist2], raised to unknown_cost when unknown_cost > 0, state == 0 and it is lower   (may be NULL)
+ * This equals the least squared distance over ALL sources of the map's window, ties to the lowest window index i' * ny + j'.
+ * The same bits every run: no atomic, no workgroup waits for another; every output is written in full.
+ * workspace: 16-byte aligned, workspace_bytes >= (4 * M * nx * ny + 15) & ~15.
+ * CRD_E_INVALID, nothing launched: NULL state, clear_table, cost_table, workspace, dist2 or nearest; clear_table, dist2, nearest or
+ * clearance not 4-byte aligned, the workspace not 16-byte aligned; M < 1; nx or ny outside 1 .. 65535; M * nx * ny >= 2^31; max_cells
+ * outside 1 .. 255; sources outside 1 .. 255; unknown_cost outside 0 .. 255; a workspace too small.
+ *
+ * crd_field_paths, one launch.  xy: fp64 [K][P][2], metres in the map frame.  n_poses: int32 [K], the poses of path k that count,
+ * taken as min(max(n_poses[k], 0), P); NULL: all P.  path_map: int32 [K], the map of path k; NULL: map 0.  origin: int64 [M][2] on the
+ * device (crd_occupancy_update's `origin`).  state, dist2, cost: the field's input and outputs, [M][nx][ny].  FAR = max_cells *
+ * max_cells + 1.  Pose p < n_poses[k] of path k with map m = path_map[k], (X, Y) its two doubles, (ox, oy) = origin[m]:
+ *   wx = floor(X / cell), wy = floor(Y / cell)
+ *   INSIDE when 0 <= m < M, X and Y are finite, and ox <= wx < ox + nx and oy <= wy < oy + ny compared as doubles (ox, oy, ox + nx and
+ *   oy + ny converted to fp64): its cell is (i, j) = (wx - ox, wy - oy), c = i * ny + j; OUTSIDE otherwise
+ *   BLOCKED when inside with cost[m][i][j] >= blocked_at, or outside with outside_blocks == 1
+ * Per path, [K]:  first_blocked int32 = the lowest blocked p, or -1;  max_cost uint8 = the largest cost over the inside poses, 0
+ * without one;  min_dist2 int32 = the least dist2 over the inside poses, FAR without one;  n_outside int32;  n_unknown int32 = the
+ * inside poses with state == 0.  pose_cell int32 [K][P] (may be NULL) = c, -1 outside, -2 for p >= n_poses[k].
+ * One wave per path; integer minimum, maximum and add over its lanes, which do not depend on any order.
+ * CRD_E_INVALID, nothing launched: NULL xy, origin, state, dist2, cost or a per-path output; xy or origin not 8-byte aligned, n_poses,
+ * path_map, dist2, first_blocked, min_dist2, n_outside, n_unknown or pose_cell not 4-byte; K or P < 1; M < 1; nx or ny outside
+ * 1 .. 65535; M * nx * ny >= 2^31; max_cells outside 1 .. 255; blocked_at outside 1 .. 255; outside_blocks neither 0 nor 1; cell not
+ * finite and positive.
+ * ------------------------------------------------------------------------------------------- */
+int crd_distance_field(const uint8_t* state, int32_t M, int32_t nx, int32_t ny, int32_t sources, int32_t max_cells, int32_t unknown_cost,
+                       const float* clear_table, const uint8_t* cost_table, void* workspace, int64_t workspace_bytes, int32_t* dist2,
+                       int32_t* nearest, float* clearance, uint8_t* cost, crd_stream_t stream);
+int crd_field_paths(const double* xy, const int32_t* n_poses, const int32_t* path_map, int32_t K, int32_t P, const int64_t* origin,
+                    uint64_t cell_f64_bits, const uint8_t* state, const int32_t* dist2, const uint8_t* cost, int32_t M, int32_t nx,
+                    int32_t ny, int32_t max_cells, int32_t blocked_at, int32_t outside_blocks, int32_t* first_blocked, uint8_t* max_cost,
+                    int32_t* min_dist2, int32_t* n_outside, int32_t* n_unknown, int32_t* pose_cell, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
