@@ -1,6 +1,6 @@
 """Raw sensors to depth, point cloud and pictures in ONE captured graph: the camera front end, the radar front end, the input
-assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid, the occupancy map and its distance field
-behind it, if asked for) and the visualiser on static buffers, replayed once per frame.
+assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid, the occupancy map, its distance field and
+the navigation field behind it, if asked for) and the visualiser on static buffers, replayed once per frame.
 
 Each stage exists on its own (camera.camera_inputs, radar.radar_inputs, batch.assemble_batch, inference.InferenceGraph,
 cloud.point_cloud, viz.Visualizer) and LivePipeline.run returns the bits of calling them one by one; what it adds is the ownership of
@@ -12,6 +12,7 @@ import torch
 
 from . import field as fld
 from . import lib as L
+from . import nav as nv
 from . import occupancy as occ
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
@@ -28,6 +29,9 @@ OCCUPANCY_OPTIONS = dict(occ.MAP_OPTIONS, nx=160, ny=160, cell=0.5, M=None, cent
 # the FieldSpec's own options (its cell is the map's), picture (True: also field.picture in cmap), paths ((K, P): also check_paths on K
 # trajectories of P poses that run(paths=) brings) with blocked_at and outside_blocks
 FIELD_OPTIONS = dict(fld.SPEC_OPTIONS, picture=False, cmap="jet", paths=None, blocked_at=253, outside_blocks=True)
+# the NavSpec's own options (its cell is the map's), goals (G: the goal points of each map that run(goals=) brings) and starts ((K, P):
+# also plan_paths from K starts that run(starts=) brings, at most P cells each) with xy (the paths' cell centres as well)
+NAV_OPTIONS = dict(nv.SPEC_OPTIONS, goals=1, starts=None, xy=True)
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -60,17 +64,27 @@ class LivePipeline:
     picture and paths=(K, P) also field.picture and field.check_paths.  It needs occupancy=, whose cell it takes.  The trajectories
     live in `paths_xy`, fp64 [K,P,2] (all NaN after construction: every pose outside), which run(paths=) fills; `path_n_poses` and
     `path_map`, int32 [K] (all P poses, map 0), are the caller's to change in place.
+    nav: None, or a dictionary of NAV_OPTIONS: the navigation field of the distance field's costmap (nav.nav_field) towards goals=G
+    goal points per map, with starts=(K, P) also nav.plan_paths.  It needs field=, whose costmap and cell it takes.  The goals live in
+    `nav_goals`, fp64 [M,G,2], and the starts in `nav_starts`, fp64 [K,2] (all NaN after construction: no goal, and every path has
+    status 2), which run(goals=, starts=) fill; `nav_n_goals`, int32 [M] (all G), and `nav_path_map`, int32 [K] (map 0), are the
+    caller's to change in place.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
     point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture], field.distance_field [, field.picture] [,
-    field.check_paths], Visualizer.render."""
+    field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None, field=None):
+                 bev=None, occupancy=None, field=None, nav=None):
         fn = "LivePipeline"
+        if nav is not None:
+            if field is None:
+                raise L.CrdError(f"{fn}: nav= needs field= (the navigation field is made from the distance field's costmap)")
+            if not isinstance(nav, dict) or not set(nav) <= set(NAV_OPTIONS):
+                raise L.CrdError(f"{fn}: nav= holds {sorted(NAV_OPTIONS)}, not {nav!r}")
         if field is not None:
             if occupancy is None:
                 raise L.CrdError(f"{fn}: field= needs occupancy= (the field is made from the map's state, with its cell)")
@@ -176,6 +190,28 @@ class LivePipeline:
                 self.path_n_poses = torch.full((K,), P, dtype=torch.int32, device=dev)
                 self.path_map = torch.zeros(K, dtype=torch.int32, device=dev)
                 self.paths_out = fld.path_outputs(K, P, device=dev)
+        self.nav_opts = None if nav is None else dict(NAV_OPTIONS, **nav)
+        self.nav_spec = None
+        if self.nav_opts is not None:
+            o, omap = self.nav_opts, self.occupancy_map
+            self.nav_spec = nv.NavSpec(omap.cell, **{k: o[k] for k in nv.SPEC_OPTIONS})
+            try:
+                G = int(o["goals"])
+                K, P = (0, 0) if o["starts"] is None else (int(v) for v in o["starts"])
+            except (TypeError, ValueError):
+                G = K = P = -1
+            if G < 1 or (o["starts"] is not None and (K < 1 or P < 1)):
+                raise L.CrdError(f"{fn}: nav goals {o['goals']!r} is G >= 1, goals per map, and starts {o['starts']!r} is None or (K, P), paths "
+                                 "and cells per path, each at least 1")
+            self.nav_ws = nv.NavWorkspace(self.nav_spec, omap.M, omap.nx, omap.ny, device=dev)
+            self.nav_goals = torch.full((omap.M, G, 2), math.nan, dtype=torch.float64, device=dev)
+            self.nav_n_goals = torch.full((omap.M,), G, dtype=torch.int32, device=dev)
+            self.nav_starts = None
+            if o["starts"] is not None:
+                self.nav_P = P
+                self.nav_starts = torch.full((K, 2), math.nan, dtype=torch.float64, device=dev)
+                self.nav_path_map = torch.zeros(K, dtype=torch.int32, device=dev)
+                self.nav_paths_out = nv.path_outputs(K, P, xy=bool(o["xy"]), device=dev)
         self.visualizer = None if viz is None else Visualizer(B, h, w, **dict({"image_order": order_out, "device": dev}, **viz))
         # the eval plan, exactly as InferenceGraph takes it
         was_training = model.training
@@ -254,6 +290,12 @@ class LivePipeline:
                         out["field"]["paths"] = dict(fld.check_paths(self.field_spec, dist, res, self.paths_xy, self.path_n_poses, self.path_map,
                                                                      blocked_at=o["blocked_at"], outside_blocks=o["outside_blocks"],
                                                                      out=self.paths_out))
+                    if self.nav_spec is not None:
+                        field_to_go = nv.nav_field(self.nav_spec, dist, res, self.nav_goals, self.nav_n_goals, workspace=self.nav_ws)
+                        out["nav"] = dict(field_to_go)
+                        if self.nav_starts is not None:
+                            out["nav"]["paths"] = dict(nv.plan_paths(self.nav_spec, field_to_go, res, self.nav_starts, self.nav_P,
+                                                                     self.nav_path_map, xy=bool(self.nav_opts["xy"]), out=self.nav_paths_out))
         if self.visualizer is not None:
             out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
         return out
@@ -272,7 +314,7 @@ class LivePipeline:
         dst.copy_(value)
 
     def run(self, frames, points=None, sweep_index=None, frame_offsets=None, cam1_from_sensor=None, cam2_from_sensor=None, lags=None, K=None,
-            out_from_cam=None, clone=False, map_from_out=None, paths=None):
+            out_from_cam=None, clone=False, map_from_out=None, paths=None, goals=None, starts=None):
         """One batch of sensor data through the graph.
 
         frames: uint8 [B,H,W,frame_channels] with any strides (a view of a capture buffer; a host tensor is copied up).  points
@@ -282,12 +324,13 @@ class LivePipeline:
         without a cloud needs none).  out_from_cam: fp64 [3,4] or [B,3,4], the cloud's frame; None: the camera's own.  map_from_out:
         fp64 [3,4] or [B,3,4], the pose of the cloud's frame in the occupancy map's frame for this batch (with occupancy= only); None:
         the identity.  paths: fp64 [K,P,2], the trajectories of this batch in the map frame (with field=dict(paths=(K, P)) only);
-        None: those of the run before.
+        None: those of the run before.  goals: fp64 [M,G,2], the goal points of this batch in the map frame (with nav= only), and
+        starts: fp64 [K,2], the starts of its planned paths (with nav=dict(starts=(K, P)) only); None: those of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'occupancy', 'field' and 'pictures' (if asked for at construction: the dictionaries of
+        output dictionary), 'cloud', 'bev', 'occupancy', 'field', 'nav' and 'pictures' (if asked for at construction: the dictionaries of
         point_cloud, of bev_grid, of occupancy.update and of field.distance_field -- each with 'picture' if asked for, the last with
-        'paths', check_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
+        'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call
         does not wait for the device."""
@@ -325,6 +368,14 @@ class LivePipeline:
             if self.field_spec is None or self.paths_xy is None:
                 raise L.CrdError("LivePipeline.run: paths goes with field=dict(paths=(K, P))")
             self._load(self.paths_xy, paths, "paths")
+        if goals is not None:
+            if self.nav_spec is None:
+                raise L.CrdError("LivePipeline.run: goals goes with nav=")
+            self._load(self.nav_goals, goals, "goals")
+        if starts is not None:
+            if self.nav_spec is None or self.nav_starts is None:
+                raise L.CrdError("LivePipeline.run: starts goes with nav=dict(starts=(K, P))")
+            self._load(self.nav_starts, starts, "starts")
         self.plan.ensure_packed()                   # optimizer step / load_state_dict / mark_params_changed() since the last frame
         self.graph.replay()
         return _copies(self._results) if clone else dict(self._results)

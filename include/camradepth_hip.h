@@ -1048,6 +1048,70 @@ int crd_field_paths(const double* xy, const int32_t* n_poses, const int32_t* pat
                     int32_t* min_dist2, int32_t* n_outside, int32_t* n_unknown, int32_t* pose_cell, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Navigation field: a costmap and goal points -> per cell the least cost to reach a goal and the neighbour to step to, as ROS navfn /
+ * global_planner give them; and the paths that follow those steps from K starts ("Navigation field").  The step after
+ * the distance field, with its conventions: no allocation, no synchronisation, capturable in a graph on one stream, arguments checked
+ * before any GPU call, fp64 scalars as IEEE-754 bit patterns.  The two entries add no struct and change no signature:
+ * CRD_ABI_VERSION stays.  Integer arithmetic only; the fp64 divide, floor and compare that find a cell and the cell centres of a path
+ * are written out below.  tests/nav_ref.py restates both entries in NumPy and the kernels agree with it bit for bit.
+ *
+ * Grid.  The window's rectangle [nx][ny], 8-connected; it does not wrap (as in crd_distance_field).  Neighbour code n = 0 .. 7 is
+ * (di, dj) = (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1); its weight k_n is 7 for a diagonal, 5 for an axis move
+ * (chamfer 5-7).  Cell c is PASSABLE when cost[m][i][j] < blocked_at.  Standing on it costs w(c) = neutral + cost[c], neutral 1 .. 255
+ * (navfn's COST_NEUTRAL is 50).  There is no corner rule: a diagonal move between two impassable cells is allowed.  With the field's
+ * inscribed >= cell the inflated walls are at least two cells thick and it cannot happen.
+ *
+ * crd_nav_field, three launches.  cost: uint8 [M][nx][ny] (crd_distance_field's `cost`, or any uint8 map).  goals: fp64 [M][G][2],
+ * metres in the map frame; n_goals: int32 [M], the goals of map m that count, taken as min(max(n_goals[m], 0), G); NULL: all G.
+ * origin: int64 [M][2] on the device.  A goal's cell is found by crd_field_paths' INSIDE rule: wx = floor(X / cell), wy = floor(Y /
+ * cell), inside when X and Y are finite and ox <= wx < ox + nx, oy <= wy < oy + ny compared as doubles; (i, j) = (wx - ox, wy - oy).
+ * A goal that is not finite, outside the window or on an impassable cell is SKIPPED.
+ *   togo  int32 [M][nx][ny]  0 on every passable goal cell; elsewhere the least, over all 8-connected paths of passable cells from the
+ *                            cell to a goal cell, of the sum of k * w(a) over every cell a of the path but the goal, k the weight of the
+ *                            move that leaves a: the unique fixed point of togo[a] = min_n (togo[a + n] + k_n * w(a)).  UNREACHED =
+ *                            0x7fffffff on impassable cells and on cells without a path.
+ *   next  uint8 [M][nx][ny]  (may be NULL)  8 on a goal cell (togo == 0), 255 where togo is UNREACHED, else the code n that minimises
+ *                            togo[a + n] + k_n * w(a) over the neighbours inside the window with togo != UNREACHED, the lowest n among
+ *                            equal ones.  A launch of its own over the final togo: a function of togo, cost and neutral alone.
+ *   info  int32 [M][4]       {converged (0 / 1), rounds, goals_used, goals_skipped}; goals_used + goals_skipped = the goals that count
+ * One step costs at most 7 * 510 = 3570 and a shortest path visits a cell once, so with nx * ny <= 2^19 per map every togo is below
+ * 3570 * 2^19 < 2^31; inside a row scan a candidate reaches at most that + 5 * 510 * 65535 < 2^31.  UNREACHED + anything is never formed.
+ * Order.  Launch 1 sets togo to UNREACHED.  Launch 2, one wave per map, sets the goal cells to 0 and relaxes in ROUNDS.  A ROW STEP of
+ * row i from row p takes t[j] = min(togo[i][j], togo[p][j + dj] + k * w(i, j) over dj = -1, 0, 1) on the passable cells, then left to
+ * right d[j] = min(t[j], d[j - 1] + 5 * w(i, j)), then right to left the same from d[j + 1], a wall or the row's end giving nothing.  A
+ * round is the row steps i = 0 .. nx - 1 from p = i - 1 (row 0 from none) and then i = nx - 2 .. 0 from p = i + 1.  Rounds end after the
+ * first that lowers no value (converged = 1: togo is the fixed point) or after max_rounds, 1 .. 4096 (converged = 0: every value is still
+ * the cost of a real path, or UNREACHED, so >= the true one; following `next` still strictly lowers togo, by at least 5 a step, so a
+ * path always ends).  rounds, 1 .. max_rounds, is informative: it belongs to this order.  The fixed point does not.
+ * The same bits every run: no atomic, no workgroup waits for another; every output is written in full.  No workspace.
+ * CRD_E_INVALID, nothing launched: NULL cost, goals, origin, togo or info; goals or origin not 8-byte aligned, n_goals, togo or info not
+ * 4-byte; M < 1; nx or ny outside 1 .. 65535; nx * ny > 2^19; M * nx * ny >= 2^31; G < 1; neutral outside 1 .. 255; blocked_at outside
+ * 1 .. 255; max_rounds outside 1 .. 4096; cell not finite and positive.
+ *
+ * crd_nav_paths, one launch, one lane per path: a path is a chain of dependent reads.  starts: fp64 [K][2], metres in the map frame.
+ * path_map: int32 [K], the map of path k; NULL: map 0; an index outside 0 .. M-1: no start cell.  togo, next: crd_nav_field's.  P >= 1:
+ * the most cells of a path.  The start cell is found by the INSIDE rule above.  From it the path steps to the neighbour next names
+ * until it stands on a cell whose next is 8, which is its last, or holds P cells.
+ *   cells       int32 [K][P]     i * ny + j of the cells from the start cell on, the goal cell included when reached; -1 behind the end
+ *   xy          fp64 [K][P][2]   (may be NULL)  the cells' centres ((double)(ox + i) + 0.5) * cell and ((double)(oy + j) + 0.5) * cell, ox +
+ *                                i an int64 sum, each operation rounded to fp64 in that order; NaN behind the end.  crd_field_paths takes it.
+ *   n_cells     int32 [K]        0 with status 2 or 3
+ *   start_togo  int32 [K]        togo of the start cell; UNREACHED without a start cell
+ *   status      int32 [K]        0 ended on a goal; 1 cut at P; 2 start not finite, outside the window or a bad map index; 3 the start
+ *                                cell is UNREACHED
+ * A next that is neither 0 .. 7 nor 8 on a reached cell, or that steps out of the window -- crd_nav_field writes neither -- ends the path
+ * with status 1.
+ * CRD_E_INVALID, nothing launched: NULL starts, origin, togo, next, cells, n_cells, start_togo or status; starts, origin or xy not 8-byte
+ * aligned, path_map, togo, cells, n_cells, start_togo or status not 4-byte; K or P < 1; K * P >= 2^30; the shapes and the cell as above.
+ * ------------------------------------------------------------------------------------------- */
+int crd_nav_field(const uint8_t* cost, int32_t M, int32_t nx, int32_t ny, const double* goals, const int32_t* n_goals, int32_t G,
+                  const int64_t* origin, uint64_t cell_f64_bits, int32_t neutral, int32_t blocked_at, int32_t max_rounds, int32_t* togo,
+                  uint8_t* next, int32_t* info, crd_stream_t stream);
+int crd_nav_paths(const double* starts, const int32_t* path_map, int32_t K, int32_t P, const int64_t* origin, uint64_t cell_f64_bits,
+                  const int32_t* togo, const uint8_t* next, int32_t M, int32_t nx, int32_t ny, int32_t* cells, double* xy, int32_t* n_cells,
+                  int32_t* start_togo, int32_t* status, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
