@@ -1,6 +1,6 @@
 """Raw sensors to depth, point cloud and pictures in ONE captured graph: the camera front end, the radar front end, the input
-assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid, the occupancy map, its distance field and
-the navigation field behind it, if asked for) and the visualiser on static buffers, replayed once per frame.
+assembly, the eval-mode network, the point-cloud back end (with the bird's-eye-view grid, the occupancy map, its objects, its distance
+field and the navigation field behind it, if asked for) and the visualiser on static buffers, replayed once per frame.
 
 Each stage exists on its own (camera.camera_inputs, radar.radar_inputs, batch.assemble_batch, inference.InferenceGraph,
 cloud.point_cloud, viz.Visualizer) and LivePipeline.run returns the bits of calling them one by one; what it adds is the ownership of
@@ -13,6 +13,7 @@ import torch
 from . import field as fld
 from . import lib as L
 from . import nav as nv
+from . import objects as obj
 from . import occupancy as occ
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
@@ -32,6 +33,8 @@ FIELD_OPTIONS = dict(fld.SPEC_OPTIONS, picture=False, cmap="jet", paths=None, bl
 # the NavSpec's own options (its cell is the map's), goals (G: the goal points of each map that run(goals=) brings) and starts ((K, P):
 # also plan_paths from K starts that run(starts=) brings, at most P cells each) with xy (the paths' cell centres as well)
 NAV_OPTIONS = dict(nv.SPEC_OPTIONS, goals=1, starts=None, xy=True)
+# the ObjectSpec's own options (its cell is the map's)
+OBJECT_OPTIONS = obj.SPEC_OPTIONS
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -69,17 +72,24 @@ class LivePipeline:
     `nav_goals`, fp64 [M,G,2], and the starts in `nav_starts`, fp64 [K,2] (all NaN after construction: no goal, and every path has
     status 2), which run(goals=, starts=) fill; `nav_n_goals`, int32 [M] (all G), and `nav_path_map`, int32 [K] (map 0), are the
     caller's to change in place.
+    objects: None, or a dictionary of OBJECT_OPTIONS: the connected obstacles of the occupancy map's `state` as a label map and a
+    table (objects.map_objects).  It needs occupancy=, whose cell it takes, and not field=.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture], field.distance_field [, field.picture] [,
+    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture] [, objects.map_objects], field.distance_field [, field.picture] [,
     field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None, field=None, nav=None):
+                 bev=None, occupancy=None, field=None, nav=None, objects=None):
         fn = "LivePipeline"
+        if objects is not None:
+            if occupancy is None:
+                raise L.CrdError(f"{fn}: objects= needs occupancy= (the objects are those of the map's state, with its cell)")
+            if not isinstance(objects, dict) or not set(objects) <= set(OBJECT_OPTIONS):
+                raise L.CrdError(f"{fn}: objects= holds {sorted(OBJECT_OPTIONS)}, not {objects!r}")
         if nav is not None:
             if field is None:
                 raise L.CrdError(f"{fn}: nav= needs field= (the navigation field is made from the distance field's costmap)")
@@ -171,6 +181,11 @@ class LivePipeline:
             self.centre = None if centre is None else torch.tensor(centre, dtype=torch.float64, device=dev)
             M = self.occupancy_map.M
             self.occupancy_picture = torch.empty(M, o["nx"], o["ny"], 3, dtype=torch.uint8, device=dev) if o["picture"] else None
+        self.object_spec = None
+        if objects is not None:
+            omap = self.occupancy_map
+            self.object_spec = obj.ObjectSpec(omap.cell, **dict(OBJECT_OPTIONS, **objects))
+            self.object_ws = obj.ObjectWorkspace(self.object_spec, omap.M, omap.nx, omap.ny, device=dev)
         self.field_opts = None if field is None else dict(FIELD_OPTIONS, **field)
         self.field_spec = None
         if self.field_opts is not None:
@@ -280,6 +295,8 @@ class LivePipeline:
                 out["occupancy"] = dict(res)
                 if self.occupancy_picture is not None:
                     out["occupancy"]["picture"] = occ.picture(res, self.occupancy_map, self.occupancy_opts["cmap"], out=self.occupancy_picture)
+                if self.object_spec is not None:
+                    out["objects"] = dict(obj.map_objects(self.object_spec, res, res, workspace=self.object_ws))
                 if self.field_spec is not None:
                     o = self.field_opts
                     dist = fld.distance_field(self.field_spec, res, workspace=self.field_ws, out=self.field_ws.out)
@@ -328,8 +345,8 @@ class LivePipeline:
         starts: fp64 [K,2], the starts of its planned paths (with nav=dict(starts=(K, P)) only); None: those of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'occupancy', 'field', 'nav' and 'pictures' (if asked for at construction: the dictionaries of
-        point_cloud, of bev_grid, of occupancy.update and of field.distance_field -- each with 'picture' if asked for, the last with
+        output dictionary), 'cloud', 'bev', 'occupancy', 'objects', 'field', 'nav' and 'pictures' (if asked for at construction: the
+        dictionaries of point_cloud, of bev_grid, of occupancy.update, of objects.map_objects and of field.distance_field -- each with 'picture' if asked for, the last with
         'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call

@@ -1112,6 +1112,51 @@ int crd_nav_paths(const double* starts, const int32_t* path_map, int32_t K, int3
                   int32_t* start_togo, int32_t* status, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Map objects: a state map -> the connected sets of its source cells as a label per cell and a table of objects ("Map
+ * objects").  A stage beside the distance field, with the conventions of the map stages: no allocation, no synchronisation, capturable
+ * in a graph on one stream, arguments checked before any GPU call, fp64 scalars as IEEE-754 bit patterns.  The entry adds no struct and
+ * changes no signature: CRD_ABI_VERSION stays.  Integer arithmetic only but the centre, which is written out below.
+ * tests/objects_ref.py restates the entry in NumPy and the kernels agree with it bit for bit.
+ *
+ * crd_map_objects, eight launches (seven with centre == NULL), whatever the map holds.  state: uint8 [M][nx][ny] in WINDOW order
+ * (crd_occupancy_update's `state`, or any uint8 map).  Cell (m, i, j) is a SOURCE when state < 8 and bit `state` of `sources` is set,
+ * as in crd_distance_field.  Two source cells of one map are NEIGHBOURS when they differ by 1 in i or in j and not in the other
+ * (connectivity 4), or by at most 1 in both (connectivity 8: cells that touch at a corner as well).  The window is a rectangle here, not
+ * the torus.  An OBJECT is a maximal set of source cells joined by chains of neighbours.  Its FIRST CELL is its lowest window index
+ * i * ny + j.  The objects of a map are ordered by their first cells (scipy.ndimage.label's numbering minus one).
+ * Objects of fewer than min_cells cells are SMALL.  The others are KEPT and numbered 0, 1, ... in that order; with N = max_objects, the
+ * kept objects with a number >= N OVERFLOW.
+ *   label    int32 [M][nx][ny]  -1 on a non-source cell, -2 on a cell of a small object, -3 on a cell of an overflowing object, else
+ *                               the object's number 0 .. N-1
+ *   objects  int32 [M][N][8]    row k: {first_cell, n_cells, i_min, i_max, j_min, j_max, flags, 0} of kept object k; flags bit 0 is set
+ *                               when a cell of the object lies in row 0 or nx - 1 or column 0 or ny - 1; unused rows are
+ *                               {-1, 0, -1, -1, -1, -1, 0, 0}
+ *   sums     int64 [M][N][2]    {sum of i, sum of j} over the object's cells; unused rows 0
+ *   centre   fp64 [M][N][2]     (may be NULL)  x = (((double)ox + (double)sum_i / (double)n_cells) + 0.5) * cell and y the same with oy and
+ *                               sum_j, (ox, oy) = origin[m], each operation rounded to fp64 in that order: the mean of crd_nav_paths' cell
+ *                               centres, which crd_field_paths and crd_nav_field's goals take as they are.  NaN (0x7ff8000000000000) in
+ *                               unused rows.  The centre of a concave object may lie off it.
+ *   info     int32 [M][4]       {n_objects = the rows in use, min(kept, N); n_overflow = the kept objects without a row; n_small; guard}
+ * origin: int64 [M][2] on the device (crd_occupancy_update's `origin`), read there, for the centre only.
+ * Every output is a function of the partition into objects alone.  Integer atomics (min, max, or, add) write the table and the
+ * counts, so no order changes a bit: the same bits every run.  No float atomic; no workgroup waits for another.
+ * Order.  Launch 1 labels tiles of 16 rows x 64 columns in LDS.  Launch 2 joins the tiles along their borders by a union-find on the
+ * parent table, which is `label`: the larger root is always hung under the smaller, so parent[c] <= c at all times and a root is a
+ * first cell; every access is an agent-scope atomic and nothing is concluded before launch 3.  Launches 3 to 7 find every cell's root,
+ * count the cells per root, number the kept roots by a count scan in index order, write label and fill the table.  Every device loop
+ * is capped: a find makes at most nx * ny steps and a union at most nx * ny retries.  A loop that reaches its cap leaves and sets guard
+ * to 1: guard is 0 in every correct run, and with 1 the map's outputs are not to be trusted.
+ * workspace: 16-byte aligned, workspace_bytes >= (8 * M * nx * ny + 15) & ~15 (a root and a count per cell).
+ * CRD_E_INVALID, nothing launched: NULL state, origin, workspace, label, objects, sums or info; label, objects or info not 4-byte
+ * aligned, sums, centre or origin not 8-byte, the workspace not 16-byte; M < 1; nx or ny outside 1 .. 65535; M * nx * ny >= 2^31;
+ * sources outside 1 .. 255; connectivity neither 4 nor 8; min_cells < 1; max_objects outside 1 .. 65535; a workspace too small; cell
+ * not finite and positive.
+ * ------------------------------------------------------------------------------------------- */
+int crd_map_objects(const uint8_t* state, int32_t M, int32_t nx, int32_t ny, int32_t sources, int32_t connectivity, int32_t min_cells,
+                    int32_t max_objects, const int64_t* origin, uint64_t cell_f64_bits, void* workspace, int64_t workspace_bytes,
+                    int32_t* label, int32_t* objects, int64_t* sums, double* centre, int32_t* info, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
