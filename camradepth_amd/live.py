@@ -15,6 +15,7 @@ from . import lib as L
 from . import nav as nv
 from . import objects as obj
 from . import occupancy as occ
+from . import tracks as trk
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
 from .cloud import CloudWorkspace, point_cloud
@@ -35,6 +36,8 @@ FIELD_OPTIONS = dict(fld.SPEC_OPTIONS, picture=False, cmap="jet", paths=None, bl
 NAV_OPTIONS = dict(nv.SPEC_OPTIONS, goals=1, starts=None, xy=True)
 # the ObjectSpec's own options (its cell is the map's)
 OBJECT_OPTIONS = obj.SPEC_OPTIONS
+# the TrackSpec's own options (the tracks take the map's shape and cell and the object table's rows)
+TRACK_OPTIONS = trk.SPEC_OPTIONS
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -74,17 +77,25 @@ class LivePipeline:
     caller's to change in place.
     objects: None, or a dictionary of OBJECT_OPTIONS: the connected obstacles of the occupancy map's `state` as a label map and a
     table (objects.map_objects).  It needs occupancy=, whose cell it takes, and not field=.
+    tracks: None, or a dictionary of TRACK_OPTIONS: the objects followed over the runs with ids that stay (tracks.track_objects on an
+    ObjectTracks, `object_tracks`, owned by this object).  It needs objects=, with max_objects <= 1024.  The tracks are empty after
+    construction; object_tracks.reset() empties them again.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture] [, objects.map_objects], field.distance_field [, field.picture] [,
+    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture] [, objects.map_objects [, tracks.track_objects]], field.distance_field [, field.picture] [,
     field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None, field=None, nav=None, objects=None):
+                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None):
         fn = "LivePipeline"
+        if tracks is not None:
+            if objects is None:
+                raise L.CrdError(f"{fn}: tracks= needs objects= (the tracks follow the rows of the object table)")
+            if not isinstance(tracks, dict) or not set(tracks) <= set(TRACK_OPTIONS):
+                raise L.CrdError(f"{fn}: tracks= holds {sorted(TRACK_OPTIONS)}, not {tracks!r}")
         if objects is not None:
             if occupancy is None:
                 raise L.CrdError(f"{fn}: objects= needs occupancy= (the objects are those of the map's state, with its cell)")
@@ -186,6 +197,12 @@ class LivePipeline:
             omap = self.occupancy_map
             self.object_spec = obj.ObjectSpec(omap.cell, **dict(OBJECT_OPTIONS, **objects))
             self.object_ws = obj.ObjectWorkspace(self.object_spec, omap.M, omap.nx, omap.ny, device=dev)
+        self.track_spec, self.object_tracks = None, None
+        if tracks is not None:
+            omap = self.occupancy_map
+            self.track_spec = trk.TrackSpec(**dict(TRACK_OPTIONS, **tracks))
+            self.object_tracks = trk.ObjectTracks(self.track_spec, omap.M, omap.nx, omap.ny, omap.cell, device=dev)
+            self.track_ws = trk.TrackWorkspace(self.track_spec, self.object_tracks, self.object_spec.max_objects)
         self.field_opts = None if field is None else dict(FIELD_OPTIONS, **field)
         self.field_spec = None
         if self.field_opts is not None:
@@ -248,6 +265,8 @@ class LivePipeline:
             if self.occupancy_map is not None:      # the warm-up pass fused a frame of zeros into the map: the first run starts empty
                 self.occupancy_map.reset()
                 self.occupancy_map.status_word.zero_()
+            if self.object_tracks is not None:      # and gave its objects tracks
+                self.object_tracks.reset()
         torch.cuda.current_stream().wait_stream(self.stream)
         model.train(was_training)
 
@@ -297,6 +316,9 @@ class LivePipeline:
                     out["occupancy"]["picture"] = occ.picture(res, self.occupancy_map, self.occupancy_opts["cmap"], out=self.occupancy_picture)
                 if self.object_spec is not None:
                     out["objects"] = dict(obj.map_objects(self.object_spec, res, res, workspace=self.object_ws))
+                    if self.track_spec is not None:
+                        out["tracks"] = dict(trk.track_objects(self.track_spec, self.object_tracks, out["objects"], res,
+                                                               workspace=self.track_ws))
                 if self.field_spec is not None:
                     o = self.field_opts
                     dist = fld.distance_field(self.field_spec, res, workspace=self.field_ws, out=self.field_ws.out)
@@ -345,8 +367,8 @@ class LivePipeline:
         starts: fp64 [K,2], the starts of its planned paths (with nav=dict(starts=(K, P)) only); None: those of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'occupancy', 'objects', 'field', 'nav' and 'pictures' (if asked for at construction: the
-        dictionaries of point_cloud, of bev_grid, of occupancy.update, of objects.map_objects and of field.distance_field -- each with 'picture' if asked for, the last with
+        output dictionary), 'cloud', 'bev', 'occupancy', 'objects', 'tracks', 'field', 'nav' and 'pictures' (if asked for at construction: the
+        dictionaries of point_cloud, of bev_grid, of occupancy.update, of objects.map_objects, of tracks.track_objects and of field.distance_field -- each with 'picture' if asked for, the last with
         'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call

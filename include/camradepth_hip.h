@@ -1157,6 +1157,66 @@ int crd_map_objects(const uint8_t* state, int32_t M, int32_t nx, int32_t ny, int
                     int32_t* label, int32_t* objects, int64_t* sums, double* centre, int32_t* info, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Object tracks: the object table of a frame and the tracks kept over the frames -> every row's track, with an id that stays
+ * ("Object tracks").  The stage behind crd_map_objects, with the conventions of the map stages: no allocation, no
+ * synchronisation, capturable in a graph on one stream, arguments checked before any GPU call, fp64 scalars as IEEE-754 bit
+ * patterns.  The entry adds no struct and changes no signature: CRD_ABI_VERSION stays.  tests/tracks_ref.py restates the entry in
+ * NumPy and the kernel agrees with it bit for bit.
+ *
+ * crd_track_objects, one launch.  objects int32 [M][N][8], centre fp64 [M][N][2], objects_info int32 [M][4]: crd_map_objects' outputs
+ * (N = its max_objects, here 1 .. 1024).  origin int64 [M][2] on the device, (ox, oy) = origin[m].  The STATE, T slots per map, is
+ * read and written in place:
+ *   ids      int64 [M][T]     the track's id, -1 in a free slot
+ *   tracks   int32 [M][T][8]  {status (0 FREE, 1 TENTATIVE, 2 CONFIRMED), age, hits, misses, object, n_cells, flags, 0}
+ *   pos      fp64 [M][T][2]   metres in the map frame, as centre;  vel fp64 [M][T][2]  metres per call
+ *   box      int64 [M][T][4]  WORLD cells {ox + i_min, ox + i_max, oy + j_min, oy + j_max} of the row last matched
+ *   next_id  int64 [M]        the id of the map's next birth
+ * A FREE slot holds ids -1, tracks {0, 0, 0, 0, -1, 0, 0, 0}, pos and vel NaN (0x7ff8000000000000), box 0; a slot is LIVE when its
+ * status is not 0.  Per map, in this order, every fp64 operation rounded to fp64 in the order written (no fused multiply-add):
+ *   1 predict     every live slot t: pred = pos + vel, per component
+ *   2 candidates  the rows k < n = min(max(objects_info[m][0], 0), N) whose centre z has two finite components.  For a live slot t and
+ *                 a candidate row k: dx = z.x - pred.x, dy = z.y - pred.y, d2 = (dx * dx) + (dy * dy); (t, k) is a PAIR when
+ *                 d2 <= gate * gate (the product rounded once; a NaN compares false)
+ *   3 associate   the greedy assignment over the pairs in ascending order of the triple (d2, t, k): a pair is TAKEN when neither its
+ *                 slot nor its row is taken yet.  Run as ROUNDS: every untaken candidate row picks its least (d2, t) over the untaken
+ *                 live slots it pairs with, every untaken live slot its least (d2, k) over the untaken rows; a row and a slot that
+ *                 picked each other are taken; the rounds end after the first that takes nothing.  The least pair left is always
+ *                 mutual, and nothing before a mutual pair in the order shares its slot or row, so this IS the sorted greedy
+ *                 assignment.  Every round but the last takes a pair, so there are at most min(N, T) + 1, which is the cap of the
+ *                 loop; leaving by the cap sets guard to 1: guard is 0 in every correct run.  rounds, 1 .. min(N, T) + 1, counts the
+ *                 last round too; it is the longest chain of displaced picks plus one and belongs to this order, the pairs do not.
+ *   4 matched     a live slot taken by row k: r = z - pred, pos = pred + alpha * r, vel = vel + beta * r (per component); hits + 1,
+ *                 misses = 0, age + 1 (hits, misses and age stop at 2^31 - 1); object = k; n_cells and flags are the row's; box from
+ *                 the row and the origin (64-bit sums); status = CONFIRMED once hits >= confirm_hits
+ *   5 unmatched   a live slot not taken: pos = pred, vel stays, misses + 1, age + 1, object = -1, n_cells, flags and box stay; with
+ *                 misses > max_misses the slot is freed (n_missed_out)
+ *   6 left        a slot still live whose pos is not INSIDE the window by crd_field_paths' rule (wx = floor(X / cell), wy = floor(Y /
+ *                 cell), X and Y finite, ox <= wx < ox + nx and oy <= wy < oy + ny compared as doubles) is freed (n_left): the map
+ *                 has forgotten that ground.  The row that had taken it keeps no track and is not born either.
+ *   7 births      the candidate rows not taken, in row order, take the free slots, in slot order, those freed by 5 and 6 included,
+ *                 rank to rank (a count scan, no ticket).  Rank r is born with ids = next_id + r, pos = z, vel = +0, hits = 1,
+ *                 misses = 0, age = 1, object = k, n_cells, flags and box from the row, status TENTATIVE, or CONFIRMED when
+ *                 confirm_hits == 1.  Rows beyond the free slots stay without a track (n_overflow).  next_id += the births.
+ * Per call:
+ *   track_of  int32 [M][N]  the slot that holds row k's track after the call (matched and still live, or born), else -1
+ *   id_of     int64 [M][N]  that slot's id, else -1
+ *   info      int32 [M][8]  {n_live (at the end), n_matched (the pairs taken), n_born, n_missed_out, n_left, n_overflow, rounds, guard}
+ * So n_live = the n_live before + n_born - n_missed_out - n_left, tracks[..][object] and track_of are inverse to each other on the
+ * live slots with object >= 0, and an id is never used twice.  Merges and splits are not modelled: when two objects grow into one, one
+ * track goes on with the joint object and the other coasts and drops.
+ * One workgroup per map, one thread per slot and per row, the predictions, the centres, the taken marks and the picks in LDS.  No
+ * atomic, no workgroup waits for another, every output written in full: the same bits every run.
+ * CRD_E_INVALID, nothing launched: NULL objects, centre, objects_info, origin, ids, tracks, pos, vel, box, next_id, track_of, id_of or
+ * info; objects, objects_info, tracks, track_of or info not 4-byte aligned, centre, origin, ids, pos, vel, box, next_id or id_of not
+ * 8-byte; M < 1; N or T outside 1 .. 1024; nx or ny outside 1 .. 65535; cell not finite and positive; gate not finite and positive or
+ * with an infinite square; alpha outside (0, 1]; beta outside [0, 2]; confirm_hits < 1; max_misses < 0.
+ * ------------------------------------------------------------------------------------------- */
+int crd_track_objects(const int32_t* objects, const double* centre, const int32_t* objects_info, const int64_t* origin, int32_t M, int32_t N,
+                      int32_t T, int32_t nx, int32_t ny, uint64_t cell_f64_bits, uint64_t gate_f64_bits, uint64_t alpha_f64_bits,
+                      uint64_t beta_f64_bits, int32_t confirm_hits, int32_t max_misses, int64_t* ids, int32_t* tracks, double* pos, double* vel,
+                      int64_t* box, int64_t* next_id, int32_t* track_of, int64_t* id_of, int32_t* info, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
