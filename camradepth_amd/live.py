@@ -12,6 +12,7 @@ import torch
 
 from . import field as fld
 from . import lib as L
+from . import match as mt
 from . import nav as nv
 from . import objects as obj
 from . import occupancy as occ
@@ -38,6 +39,8 @@ NAV_OPTIONS = dict(nv.SPEC_OPTIONS, goals=1, starts=None, xy=True)
 OBJECT_OPTIONS = obj.SPEC_OPTIONS
 # the TrackSpec's own options (the tracks take the map's shape and cell and the object table's rows)
 TRACK_OPTIONS = trk.SPEC_OPTIONS
+# the MatchSpec's own options (the matcher takes the map, its cell and its min_points unless given)
+MATCH_OPTIONS = mt.SPEC_OPTIONS
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -80,17 +83,25 @@ class LivePipeline:
     tracks: None, or a dictionary of TRACK_OPTIONS: the objects followed over the runs with ids that stay (tracks.track_objects on an
     ObjectTracks, `object_tracks`, owned by this object).  It needs objects=, with max_objects <= 1024.  The tracks are empty after
     construction; object_tracks.reset() empties them again.
+    match: None, or a dictionary of MATCH_OPTIONS: the pose run(map_from_out=) brings is corrected against the occupancy map as it stands
+    (match.match_scan) before the cloud is fused, and the update reads the corrected pose.  It needs occupancy=.  The first run finds
+    the map empty and passes the pose through, with match.UNINITIALISED in its status.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, bev_grid [, bev.picture], occupancy.update [, occupancy.picture] [, objects.map_objects [, tracks.track_objects]], field.distance_field [, field.picture] [,
+    point_cloud, bev_grid [, bev.picture] [, match.match_scan], occupancy.update [, occupancy.picture] [, objects.map_objects [, tracks.track_objects]], field.distance_field [, field.picture] [,
     field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None):
+                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None, match=None):
         fn = "LivePipeline"
+        if match is not None:
+            if occupancy is None:
+                raise L.CrdError(f"{fn}: match= needs occupancy= (the pose is matched against the map)")
+            if not isinstance(match, dict) or not set(match) <= set(MATCH_OPTIONS):
+                raise L.CrdError(f"{fn}: match= holds {sorted(MATCH_OPTIONS)}, not {match!r}")
         if tracks is not None:
             if objects is None:
                 raise L.CrdError(f"{fn}: tracks= needs objects= (the tracks follow the rows of the object table)")
@@ -192,6 +203,10 @@ class LivePipeline:
             self.centre = None if centre is None else torch.tensor(centre, dtype=torch.float64, device=dev)
             M = self.occupancy_map.M
             self.occupancy_picture = torch.empty(M, o["nx"], o["ny"], 3, dtype=torch.uint8, device=dev) if o["picture"] else None
+        self.match_spec = None
+        if match is not None:
+            self.match_spec = mt.MatchSpec(device=dev, **dict(MATCH_OPTIONS, **match))
+            self.match_ws = mt.MatchWorkspace(self.occupancy_map, self.match_spec, B)
         self.object_spec = None
         if objects is not None:
             omap = self.occupancy_map
@@ -309,7 +324,12 @@ class LivePipeline:
                 if self.bev_picture is not None:
                     out["bev"]["picture"] = picture(grid, o["picture_z_range"], o["cmap"], out=self.bev_picture)
             if self.occupancy_map is not None:
-                res = occ.update(self.occupancy_map, out["cloud"], map_from_points=self.map_from_out, sensor=self.sensor, centre=self.centre,
+                pose = self.map_from_out
+                if self.match_spec is not None:
+                    out["match"] = dict(mt.match_scan(self.occupancy_map, self.match_spec, out["cloud"], map_from_points=pose, sensor=self.sensor,
+                                                      workspace=self.match_ws))
+                    pose = out["match"]["pose"]
+                res = occ.update(self.occupancy_map, out["cloud"], map_from_points=pose, sensor=self.sensor, centre=self.centre,
                                  workspace=self.occupancy_ws, out=self.occupancy_ws.out)
                 out["occupancy"] = dict(res)
                 if self.occupancy_picture is not None:
@@ -367,8 +387,8 @@ class LivePipeline:
         starts: fp64 [K,2], the starts of its planned paths (with nav=dict(starts=(K, P)) only); None: those of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'occupancy', 'objects', 'tracks', 'field', 'nav' and 'pictures' (if asked for at construction: the
-        dictionaries of point_cloud, of bev_grid, of occupancy.update, of objects.map_objects, of tracks.track_objects and of field.distance_field -- each with 'picture' if asked for, the last with
+        output dictionary), 'cloud', 'bev', 'match', 'occupancy', 'objects', 'tracks', 'field', 'nav' and 'pictures' (if asked for at construction: the
+        dictionaries of point_cloud, of bev_grid, of match.match_scan, of occupancy.update, of objects.map_objects, of tracks.track_objects and of field.distance_field -- each with 'picture' if asked for, the last with
         'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call

@@ -1217,6 +1217,71 @@ int crd_track_objects(const int32_t* objects, const double* centre, const int32_
                       int64_t* box, int64_t* next_id, int32_t* track_of, int64_t* id_of, int32_t* info, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scan matcher: a cloud, its prior pose and the occupancy map as it stands -> the pose corrected by the best of a window of turns and
+ * whole-cell shifts ("Scan matching"; correlative scan matching, Olson, ICRA 2009).  The stage in front of
+ * crd_occupancy_update, with the conventions of the map stages: no allocation, no synchronisation, capturable in a graph on one
+ * stream, arguments checked before any GPU call, fp64 scalars as IEEE-754 bit patterns.  The entry adds no struct and changes no
+ * signature: CRD_ABI_VERSION stays.  The device only adds, multiplies, divides, floors and compares, every operation rounded on its own;
+ * tests/match_ref.py restates the entry in NumPy and the kernels agree with it bit for bit.  The map is READ ONLY here.
+ *
+ * Rows: xyz, valid, frame_offsets, rows_per_frame, B, n_rows exactly as for crd_bev_grid.  map_from_points (the prior pose, T_b),
+ * t_stride, sensor, sensor_stride, M, nx, ny, cell, max_range, z_lo, z_hi, min_points: as for crd_occupancy_update, the numbers those of
+ * the map.  map int16 [M][nx][ny] (the torus), cur_origin int64 [M][2], initialised int32 [M]: the map's state, as the last update left
+ * it.  M == B: frame b is matched against map b; M == 1: all frames against map 0, with one correction for all.
+ *
+ * Candidates.  t in 0 .. 2 * n_theta, dx and dy in -n_xy .. n_xy (whole cells); n_xy 0 .. 16, n_theta 0 .. 32; NT = 2 * n_theta + 1,
+ * NS = 2 * n_xy + 1.  rot fp64 [NT][2] on the device: (c, s) = (cos, sin) of the turn of t, (t - n_theta) * d_theta, made on the host;
+ * the row of t = n_theta is not read.
+ * The candidate pose T'[b][t] turns T = T_b (NULL: the identity) about the vertical axis of the map frame through S = T_f . sensor_f,
+ * f = b (M == B) or 0 (M == 1).  With (c, s) = rot[t], for k = 0, 1, 2:
+ *   R'[0][k] = c * T[0][k] - s * T[1][k];   R'[1][k] = s * T[0][k] + c * T[1][k];   row 2 of T is copied
+ *   t'x = (c * T[0][3] - s * T[1][3]) + (Sx - (c * Sx - s * Sy));   t'y = (s * T[0][3] + c * T[1][3]) + (Sy - (s * Sx + c * Sy))
+ * and T'[b][n_theta] is T itself, copied: the zero candidate sees exactly the cells crd_occupancy_update would.
+ * Scan cells.  A row is an obstacle row when it passes steps 1 to 3 of crd_occupancy_update's launch 2 and z_lo <= Z <= z_hi, all with
+ * the unturned T_b and S_b.  For every t an obstacle row counts into world cell (floor(X_t / cell), floor(Y_t / cell)), (X_t, Y_t)
+ * rows 0 and 1 of T'[b][t] . (x, y, z) summed left to right, when that cell lies in the window of its map grown by n_xy cells on every
+ * side, ox - n_xy <= wx < ox + nx + n_xy and oy - n_xy <= wy < oy + ny + n_xy compared as doubles, (ox, oy) = cur_origin[m] (cells
+ * farther out meet the map under no shift).  A cell is a SCAN CELL of (m, t) when its count reaches min_points.
+ * Map value.  L(wx, wy) = map[m][wx mod nx][wy mod ny] (the mathematical modulo) when initialised[m] != 0 and ox <= wx < ox + nx and
+ * oy <= wy < oy + ny; otherwise 0.
+ * Score.  table[m][t][dx + n_xy][dy + n_xy] = the sum of L(wx + dx, wy + dy) over the scan cells (wx, wy) of (m, t), in 64-bit integers.
+ * Pick.  The candidate with the largest score; among equals the least dx * dx + dy * dy, then the least |t - n_theta|, then the least
+ * t, then dx, then dy.  A symmetric scene keeps the prior.
+ * status int32 [M], this call's alone: 1 initialised[m] == 0; 2 an entry of T_b or a component of S_b of a frame that feeds the map is
+ * not finite; 4 n_cells[m] < min_cells, n_cells[m] the scan cells of (m, n_theta) inside the window itself; 8 the pick's score <
+ * min_score.  Each of these four KEEPS THE PRIOR.  16, only when none of them is set: the pick lies on the border of a search range
+ * that is not empty (|dx| or |dy| == n_xy > 0, or |t - n_theta| == n_theta > 0); the pose is applied all the same.
+ * Outputs, written in full:
+ *   pose         fp64 [B][3][4]  T'[b][t*] with t'x + dx* * cell and t'y + dy* * cell (dx*, dy* converted to fp64, the product rounded,
+ *                                then the sum); T_b itself, copied, when the map keeps the prior
+ *   pick         int32 [M][3]    (t* - n_theta, dx*, dy*), the best candidate whether it is applied or not;  score int64 [M], its score
+ *   prior_score  int64 [M]       table[m][n_theta][n_xy][n_xy];   n_cells int32 [M]
+ *   scores       int64 [M][NT][NS][NS], the table; may be NULL
+ * Four launches: prepare (T', S, clears), points (one thread per row, every turn, an integer atomic add per run of neighbouring lanes
+ * that share a cell), scores (a workgroup per tile of 32 x 32 count cells, turn and map: the tile's scan cells compacted, the log-odds
+ * under it with a halo of n_xy cells in LDS, a thread per shift, one 64-bit atomic add per shift), pick (a workgroup per map).  Integer
+ * atomics only and a pick that is the least element of a total order: the same bits every run.  No workgroup waits for another.
+ * workspace, 16-byte aligned, each part from the next multiple of 16 bytes: T' fp64 [B][NT][3][4]; S fp64 [B][3]; the counts int32
+ * [M][NT][nx + 2 n_xy][ny + 2 n_xy]; the table int64 [M][NT][NS][NS]:
+ *   workspace_bytes >= ((96 * B * NT + 15) & ~15) + ((24 * B + 15) & ~15) + ((4 * M * NT * (nx + 2 n_xy) * (ny + 2 n_xy) + 15) & ~15)
+ *                      + ((8 * M * NT * NS * NS + 15) & ~15).
+ * CRD_E_INVALID, nothing launched: NULL workspace, map, cur_origin, initialised, rot, pose, pick, score, prior_score, n_cells or status,
+ * NULL xyz with n_rows > 0; xyz, frame_offsets, initialised, pick, n_cells or status not 4-byte aligned, map not 2-byte,
+ * map_from_points, sensor, cur_origin, rot, pose, score, prior_score or scores not 8-byte, the workspace not 16-byte aligned; B outside
+ * 1 .. 65535; n_rows < 0; M neither B nor 1; nx or ny outside 1 .. 65535; M * nx * ny >= 2^31; n_xy outside 0 .. 16; n_theta outside
+ * 0 .. 32; 2^31 counts or more; cell not finite and positive; max_range not positive or its square not finite; a NaN z bound or not
+ * z_lo <= z_hi; t_stride not 0 or 12; sensor_stride not 0 or 3; both or neither of frame_offsets and rows_per_frame; min_points < 1;
+ * min_cells < 0; a workspace too small.
+ * ------------------------------------------------------------------------------------------- */
+int crd_match_scan(const float* xyz, const uint8_t* valid, const int32_t* frame_offsets, int32_t rows_per_frame, int32_t B, int32_t n_rows,
+                   const double* map_from_points, int32_t t_stride, const double* sensor, int32_t sensor_stride, int32_t M, int32_t nx,
+                   int32_t ny, uint64_t cell_f64_bits, uint64_t max_range_f64_bits, uint64_t z_lo_f64_bits, uint64_t z_hi_f64_bits,
+                   int32_t min_points, const int16_t* map, const int64_t* cur_origin, const int32_t* initialised, int32_t n_xy,
+                   int32_t n_theta, const double* rot, int32_t min_cells, int64_t min_score, void* workspace, int64_t workspace_bytes,
+                   double* pose, int32_t* pick, int64_t* score, int64_t* prior_score, int32_t* n_cells, int32_t* status, int64_t* scores,
+                   crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
