@@ -141,6 +141,7 @@ _SIGS = {
     "crd_fp8_scale_update": "ppifip", "crd_quant_fp8_dev": "pliiipiipp", "crd_tune_conv3x3_small_grid": "i", "crd_tune_igemm_reg_epilogue": "i", "crd_conv_wgrad": "pp", "crd_conv_wgrad_splits": "p", "crd_conv_wgrad_route": "ppi", "crd_wgrad_group_build": "piplp", "crd_conv_wgrad_grouped": "ppp",
     "crd_gn_stats": "piiiiiippp", "crd_gn_apply": "piiiiiipippipPiiip".replace("P", "p"),
     "crd_gn_bwd_reduce": "piiipiiiiiipippippplp", "crd_gn_bwd_apply": "piiipiiiiiipippipppppiiiipipp",
+    "crd_gn_launch_shape": "iiiippp",
     "crd_dwconv3x3": "piiiippipppippppppp", "crd_dwconv3x3_wgrad": "ppiiiipipippp",
     "crd_attn_scores": "ppiiiiifppp", "crd_attn_scores_fp8": "ppiiiiffppp", "crd_attn_fwd": "ppiiiiifpppppppppp", "crd_attn_xbar": "ppppiiipp", "crd_attn_xbar_proj": "pppppiiippp", "crd_attn_vec_bwd": "ppiiifppp", "crd_attn_out_residual": "pppppiiipp", "crd_attn_out_residual_stats": "pppppiiippp",
     "crd_attn_out_bwd": "ppppiiipppp", "crd_attn_out_bwd_blocks": "iii", "crd_attn_out_bwd_gn": "ppppiiippppppppppp", "crd_attn_scores_bwd": "ppppiiiiifpppp", "crd_attn_bwd": "ppppiiiiifpppppifppp", "crd_attn_scores_bwd_partials": "iiiii", "crd_sum_partials_bf16": "pilplp", "crd_gsum_to_bf16": "pplp",
@@ -251,6 +252,15 @@ def wgrad_route(desc):
     buf = C.create_string_buffer(96)
     check(load().crd_conv_wgrad_route(C.byref(desc), buf, len(buf)), "crd_conv_wgrad_route")
     return buf.value.decode()
+
+
+def gn_launch_shape(P, Cn, B, kind):
+    """(nblk, chunk, batch_pixels) of crd_gn_apply (kind 0) / crd_gn_bwd_apply (kind 1) for B samples of P pixels and Cn channels
+    (crd_gn_launch_shape: host arithmetic, no GPU)."""
+    out = (C.c_int32 * 3)()
+    ptr = [C.cast(C.byref(out, 4 * i), C.c_void_p) for i in range(3)]
+    check(load().crd_gn_launch_shape(P, Cn, B, kind, *ptr), "crd_gn_launch_shape")
+    return out[0], out[1], out[2]
 
 
 def stream():

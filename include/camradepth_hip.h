@@ -357,6 +357,13 @@ int crd_gn_bwd_apply(const void* x, int32_t x_f32, int32_t x_ld, int32_t x_coff,
                      const crd_sum_t* r, float* dgamma, float* dbeta, void* dx, int32_t dx_f32, int32_t dx_ld,
                      int32_t dx_coff, int32_t dx_accumulate, void* dx2, int32_t dx2_ld, const float* scale2,
                      crd_stream_t stream);
+/* The partition the two elementwise passes use for B samples of P pixels and C channels (host arithmetic, no GPU): kind 0 =
+ * crd_gn_apply / crd_gn_apply_fp8, kind 1 = crd_gn_bwd_apply / crd_gn_bwd_apply_fp8.  Each sample is cut into *nblk workgroups of
+ * *chunk pixels (the last takes what is left); *batch_pixels is what a workgroup's lanes request at once.  Grids that would
+ * leave CUs idle get fewer pixels per lane; every other grid gets chunks that are whole batches, at most 2048 workgroups in all
+ * (or B, if that is more).  The results of the passes do not depend on the partition; the tests pin through this entry which
+ * edges of it a shape runs.  A new entry, no changed signature: CRD_ABI_VERSION stays. */
+int crd_gn_launch_shape(int32_t P, int32_t C, int32_t B, int32_t kind, int32_t* nblk, int32_t* chunk, int32_t* batch_pixels);
 
 
 /* ---------------------------------------------------------------------------------------------
