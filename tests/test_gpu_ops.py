@@ -291,7 +291,9 @@ def test_groupnorm_forward_backward(C_, gmul, xf32, act):
     assert torch.equal(dx2[..., :C_], (dxf * sc2.view(B, 1, 1)).to(torch.bfloat16))
 
 
-@pytest.mark.parametrize("C_,H,W", [(64, 9, 13), (512, 8, 12), (160, 5, 7), (64, 11, 45), (80, 9, 33), (256, 17, 64)])
+@pytest.mark.parametrize("C_,H,W", [(64, 9, 13), (512, 8, 12), (160, 5, 7), (64, 11, 45), (80, 9, 33), (256, 17, 64),
+                                    # degenerate images, the W = 16 / 17 tile-width switch, whole 8-row tiles +- 1, a lone partial channel window
+                                    (16, 1, 1), (48, 3, 1), (80, 1, 17), (64, 8, 16), (64, 9, 17), (64, 16, 32), (64, 17, 33)])
 def test_dwconv(C_, H, W):
     lib, lb = L()
     g = torch.Generator().manual_seed(2)
@@ -325,7 +327,7 @@ def test_dwconv(C_, H, W):
         assert_close(tot[9], b.grad, "dwconv db", rel=2e-3, elem=4e-3)
 
 
-@pytest.mark.parametrize("C_,H,W,gmul", [(64, 9, 13, 1), (256, 17, 40, 4), (80, 8, 33, 1), (1024, 66, 20, 4)])
+@pytest.mark.parametrize("C_,H,W,gmul", [(64, 9, 13, 1), (256, 17, 40, 4), (80, 8, 33, 1), (1024, 66, 20, 4), (80, 1, 17, 1), (64, 8, 16, 1)])
 def test_dwconv_with_fused_input_groupnorm(C_, H, W, gmul):
     """in_stats != NULL: GroupNorm of the input applied while the halo is staged == crd_gn_apply followed by the plain
     kernel, bit for bit (forward, statistics and weight gradient).  The last shape (B = 4) puts the weight gradient on runs of two
