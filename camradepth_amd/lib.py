@@ -164,6 +164,7 @@ _SIGS = {
     "crd_map_objects": "piiiiiiipLplpppppp",
     "crd_track_objects": "pppp" "iiiii" "LLLL" "ii" "ppppppppp" "p",
     "crd_match_scan": "ppp" "iii" "pipi" "iii" "LLLL" "i" "ppp" "ii" "p" "il" "pl" "ppppppp" "p",
+    "crd_plan_rollouts": "pppp" "iiii" "pLpp" "iiii" "ppp" "iii" "LL" "pLL" "iiiii" "pl" "pppp" "ppppp" "p" "p",
     "crd_viz_range": "piiiiipplpp", "crd_viz_draw": "piiiippffipiiffipllp", "crd_seg_labels": "piiiipp",
     "crd_camera_frontend": "piiiilliiippip",
     "crd_resize_nearest_u8":"piiiipiip", "crd_resize_labels_nearest": "piiiipiip", "crd_seg_confusion": "ppiilppp",

@@ -16,6 +16,7 @@ from . import match as mt
 from . import nav as nv
 from . import objects as obj
 from . import occupancy as occ
+from . import rollout as ro
 from . import tracks as trk
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
@@ -41,6 +42,8 @@ OBJECT_OPTIONS = obj.SPEC_OPTIONS
 TRACK_OPTIONS = trk.SPEC_OPTIONS
 # the MatchSpec's own options (the matcher takes the map, its cell and its min_points unless given)
 MATCH_OPTIONS = mt.SPEC_OPTIONS
+# the RolloutSpec's own options but cell, which is the map's, tables (the per-candidate tables as well) and xy (the rollouts in the map frame)
+ROLLOUT_OPTIONS = dict({k: v for k, v in ro.SPEC_OPTIONS.items() if k != "cell"}, tables=False, xy=False)
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -87,16 +90,25 @@ class LivePipeline:
     (match.match_scan) before the cloud is fused, and the update reads the corrected pose.  It needs occupancy=.  The first run finds
     the map empty and passes the pose through, with match.UNINITIALISED in its status.
     viz: None, or a dictionary of Visualizer's options (image_order is order_out unless given).
+    rollout: None, or a dictionary of ROLLOUT_OPTIONS: the local planner (rollout.plan_rollouts) on the distance field's costmap, with
+    the cost-to-go of nav= and the tracks of tracks= when they are there, from the pose the occupancy update read (the matcher's with
+    match=; frame 0's when the frames share one map).  It needs field=, whose cell it takes.  With accel= the current (v, w) lives in
+    `rollout_twist`, fp64 [M,2] (zeros after construction), which run(twist=) fills.
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
     point_cloud, bev_grid [, bev.picture] [, match.match_scan], occupancy.update [, occupancy.picture] [, objects.map_objects [, tracks.track_objects]], field.distance_field [, field.picture] [,
-    field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render."""
+    field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render [, rollout.plan_rollouts]."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None, match=None):
+                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None, match=None, rollout=None):
         fn = "LivePipeline"
+        if rollout is not None:
+            if field is None:
+                raise L.CrdError(f"{fn}: rollout= needs field= (the rollouts are tested on the distance field's costmap)")
+            if not isinstance(rollout, dict) or not set(rollout) <= set(ROLLOUT_OPTIONS):
+                raise L.CrdError(f"{fn}: rollout= holds {sorted(ROLLOUT_OPTIONS)}, not {rollout!r}")
         if match is not None:
             if occupancy is None:
                 raise L.CrdError(f"{fn}: match= needs occupancy= (the pose is matched against the map)")
@@ -259,6 +271,15 @@ class LivePipeline:
                 self.nav_starts = torch.full((K, 2), math.nan, dtype=torch.float64, device=dev)
                 self.nav_path_map = torch.zeros(K, dtype=torch.int32, device=dev)
                 self.nav_paths_out = nv.path_outputs(K, P, xy=bool(o["xy"]), device=dev)
+        self.rollout_spec = None
+        if rollout is not None:
+            o, omap = dict(ROLLOUT_OPTIONS, **rollout), self.occupancy_map
+            self.rollout_opts = o
+            self.rollout_spec = ro.RolloutSpec(device=dev, cell=omap.cell, **{k: o[k] for k in ro.SPEC_OPTIONS if k != "cell"})
+            self.rollout_ws = ro.RolloutWorkspace(self.rollout_spec, omap.M, tables=bool(o["tables"]), xy=bool(o["xy"]))
+            self.rollout_twist = None
+            if self.rollout_spec.accel is not None:
+                self.rollout_twist = torch.zeros(omap.M, 2, dtype=torch.float64, device=dev)
         self.visualizer = None if viz is None else Visualizer(B, h, w, **dict({"image_order": order_out, "device": dev}, **viz))
         # the eval plan, exactly as InferenceGraph takes it
         was_training = model.training
@@ -357,6 +378,11 @@ class LivePipeline:
                                                                      self.nav_path_map, xy=bool(self.nav_opts["xy"]), out=self.nav_paths_out))
         if self.visualizer is not None:
             out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
+        if self.rollout_spec is not None:
+            o, M = self.rollout_opts, self.occupancy_map.M
+            out["rollout"] = dict(ro.plan_rollouts(self.rollout_spec, pose[:M], out["field"], out["occupancy"], nav_result=out.get("nav"),
+                                                   tracks=self.object_tracks, twist=self.rollout_twist, workspace=self.rollout_ws,
+                                                   tables=bool(o["tables"]), xy=bool(o["xy"])))
         return out
 
     def _load(self, buf, value, what, rows=False):
@@ -373,7 +399,7 @@ class LivePipeline:
         dst.copy_(value)
 
     def run(self, frames, points=None, sweep_index=None, frame_offsets=None, cam1_from_sensor=None, cam2_from_sensor=None, lags=None, K=None,
-            out_from_cam=None, clone=False, map_from_out=None, paths=None, goals=None, starts=None):
+            out_from_cam=None, clone=False, map_from_out=None, paths=None, goals=None, starts=None, twist=None):
         """One batch of sensor data through the graph.
 
         frames: uint8 [B,H,W,frame_channels] with any strides (a view of a capture buffer; a host tensor is copied up).  points
@@ -384,12 +410,13 @@ class LivePipeline:
         fp64 [3,4] or [B,3,4], the pose of the cloud's frame in the occupancy map's frame for this batch (with occupancy= only); None:
         the identity.  paths: fp64 [K,P,2], the trajectories of this batch in the map frame (with field=dict(paths=(K, P)) only);
         None: those of the run before.  goals: fp64 [M,G,2], the goal points of this batch in the map frame (with nav= only), and
-        starts: fp64 [K,2], the starts of its planned paths (with nav=dict(starts=(K, P)) only); None: those of the run before.
+        starts: fp64 [K,2], the starts of its planned paths (with nav=dict(starts=(K, P)) only); None: those of the run before.  twist: fp64 [M,2], the vehicle's current (v, w)
+        (with rollout=dict(accel=(a_v, a_w)) only); None: that of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'match', 'occupancy', 'objects', 'tracks', 'field', 'nav' and 'pictures' (if asked for at construction: the
+        output dictionary), 'cloud', 'bev', 'match', 'occupancy', 'objects', 'tracks', 'field', 'nav', 'pictures' and 'rollout' (if asked for at construction: the
         dictionaries of point_cloud, of bev_grid, of match.match_scan, of occupancy.update, of objects.map_objects, of tracks.track_objects and of field.distance_field -- each with 'picture' if asked for, the last with
-        'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary -- and of Visualizer.render).  They are VIEWS of this
+        'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary --, of Visualizer.render and of rollout.plan_rollouts).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call
         does not wait for the device."""
@@ -435,6 +462,10 @@ class LivePipeline:
             if self.nav_spec is None or self.nav_starts is None:
                 raise L.CrdError("LivePipeline.run: starts goes with nav=dict(starts=(K, P))")
             self._load(self.nav_starts, starts, "starts")
+        if twist is not None:
+            if self.rollout_spec is None or self.rollout_twist is None:
+                raise L.CrdError("LivePipeline.run: twist goes with rollout=dict(accel=(a_v, a_w))")
+            self._load(self.rollout_twist, twist, "twist")
         self.plan.ensure_packed()                   # optimizer step / load_state_dict / mark_params_changed() since the last frame
         self.graph.replay()
         return _copies(self._results) if clone else dict(self._results)

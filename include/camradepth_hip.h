@@ -1289,6 +1289,74 @@ int crd_match_scan(const float* xyz, const uint8_t* valid, const int32_t* frame_
                    crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Local planner: the vehicle's pose, the costmap, the cost-to-go and the object tracks -> a velocity command, the best of K velocity
+ * candidates rolled out over a short horizon ("Local planner"; the dynamic window approach of Fox, Burgard and Thrun,
+ * 1997, as ROS base_local_planner / dwa_local_planner run it).  The stage behind the map stages, with their conventions: no
+ * allocation, no synchronisation, capturable in a graph on one stream, arguments checked before any GPU call, fp64 scalars as IEEE-754
+ * bit patterns.  The entry adds no struct and changes no signature: CRD_ABI_VERSION stays.  The device only adds, subtracts,
+ * multiplies, divides, floors and compares, every operation rounded to fp64 on its own (no fused multiply-add); the sines and cosines
+ * of the arcs are in a table made on the host.  tests/rollout_ref.py restates the entry in NumPy and the kernels agree with it bit for
+ * bit.  Every input is READ ONLY.
+ *
+ * crd_plan_rollouts, two launches.  Candidates k = iv * n_w + iw, iv in 0 .. n_v - 1 (n_v 1 .. 64), iw in 0 .. n_w - 1 (n_w odd,
+ * 1 .. 129), c = (n_w - 1) / 2, K = n_v * n_w <= 4096.  P poses per candidate, 1 .. 256.  Tables on the device, made on the host:
+ *   vw   fp64 [K][2]     the candidate's velocities (v, w)
+ *   arc  fp64 [K][P][2]  (x, y), the pose of candidate k at time (p + 1) * dt in the vehicle's frame (x forward, y left)
+ *   tau  fp64 [P]        (p + 1) * dt in track updates
+ * pose fp64 [M][3][4], T = pose[m]: the map-from-vehicle pose; rows 0 and 1 are used.  origin int64 [M][2], cost uint8 [M][nx][ny]:
+ * as for crd_field_paths.  togo int32 [M][nx][ny], crd_nav_field's; may be NULL.  tracks int32 [M][T][8], pos and vel fp64 [M][T][2]:
+ * crd_track_objects' state, T 1 .. 1024; tracks may be NULL with T = 0.  twist fp64 [M][2], the current (v, w); may be NULL.
+ * For map m, candidate k and pose p, with (x, y) = arc[k][p], in this order:
+ *   Map-frame pose.  X = T[0][0] * x + T[0][1] * y + T[0][3] and Y = T[1][0] * x + T[1][1] * y + T[1][3], summed left to right.
+ *   Static test.  crd_field_paths' rule: wx = floor(X / cell), wy = floor(Y / cell); INSIDE when X and Y are finite and ox <= wx <
+ *     ox + nx and oy <= wy < oy + ny compared as doubles, its cell (i, j) = (wx - ox, wy - oy); BLOCKED when inside with
+ *     cost[m][i][j] >= blocked_at, or outside with outside_blocks == 1.
+ *   Track test.  Slot s of map m COUNTS when tracks[m][s][0] (status) >= min_status, the two components of pos[m][s] and of
+ *     vel[m][s] are finite, tracks[m][s][5] (n_cells) <= max_object_cells and vel_x * vel_x + vel_y * vel_y >= min_speed2.  For a
+ *     counting slot: qx = pos_x + vel_x * tau[p], qy = pos_y + vel_y * tau[p], dx = X - qx, dy = Y - qy, d2 = dx * dx + dy * dy; the
+ *     pose is HIT by s when d2 <= keep_out2 (a NaN compares false).
+ * Per candidate:
+ *   first_blocked  the lowest p that is blocked or hit by a counting slot, or -1
+ *   first_track    the lowest slot that hits the lowest hit pose, whether or not an earlier pose is blocked, or -1
+ *   max_cost, sum_cost  the largest and the sum of cost over the inside poses; 0 without one
+ *   end_togo       togo[m][cell of pose P - 1]; UNREACHED = 0x7fffffff when that pose is outside or togo is NULL
+ *   ADMISSIBLE     twist is NULL, or |vw[k][0] - twist[m][0]| <= a_v_dt and |vw[k][1] - twist[m][1]| <= a_w_dt (a NaN compares false)
+ *   CLEAR_STATIC   no pose is blocked;  CLEAR  first_blocked == -1
+ *   VALID          admissible, clear, and not (togo given, w_togo > 0 and end_togo == UNREACHED)
+ *   score  int64   w_togo * end_togo (left out when togo is NULL) + w_max_cost * max_cost + w_sum_cost * sum_cost
+ *                  + w_slow * (n_v - 1 - iv) + w_turn * |iw - c|; each weight 0 .. 32767
+ * Pick, per map: the valid candidate of least score; among equals the least |iw - c|, then the larger iv, then the least k.
+ * status: 1 NOT_FINITE, one of the 12 entries of pose[m] or, with a twist, of the 2 of twist[m] is not finite; 2 NO_CANDIDATE, no
+ * candidate is valid.  A candidate is picked when status is 0.
+ * Outputs, written in full:
+ *   best     int32 [M]     the picked k, or -1;   score int64 [M]  its score, or 0
+ *   command  fp64 [M][2]   vw[best] copied, or (+0.0, +0.0): the vehicle stops
+ *   info     int32 [M][8]  {n_admissible, n_clear_static, n_clear, n_valid, status, 0, 0, 0}, each count over all K candidates
+ *   scores int64, first_blocked, first_track, max_cost, end_togo int32, each [M][K]: the per-candidate values; all five or all NULL
+ *   xy       fp64 [M][K][P][2]  (X, Y) of every pose; may be NULL.  crd_field_paths takes a map's [K][P][2] as it is.
+ * Launch 1, rollouts: one wave per (candidate, map), four to a workgroup, the lanes over the poses; the workgroup first compacts the
+ * counting slots of its map into LDS by ballot, in slot order, and every lane walks that list; integer minimum, maximum and add over
+ * the wave; one record per candidate into the workspace.  Launch 2, pick: one workgroup per map.  No global atomic and a pick that is
+ * the least element of a total order: the same bits every run.  No workgroup waits for another.
+ * workspace: 16-byte aligned, workspace_bytes >= 32 * M * K (a record of 32 bytes per candidate).
+ * CRD_E_INVALID, nothing launched: NULL pose, vw, arc, tau, origin, cost, workspace, best, command, score or info; tracks without pos
+ * or vel; some but not all of the five tables; pose, vw, arc, tau, origin, pos, vel, twist, command, score, scores or xy not 8-byte
+ * aligned, togo, tracks, best, info, first_blocked, first_track, max_cost or end_togo not 4-byte, the workspace not 16-byte; M outside
+ * 1 .. 65535; n_v outside 1 .. 64; n_w even or outside 1 .. 129; K > 4096; P outside 1 .. 256; nx or ny outside 1 .. 65535; M * nx * ny
+ * >= 2^31; blocked_at outside 1 .. 255; outside_blocks neither 0 nor 1; cell not finite and positive; min_speed2 or keep_out2 negative
+ * or not finite; with a twist a_v_dt or a_w_dt negative or NaN; T outside 0 .. 1024, T > 0 without tracks or T == 0 with them;
+ * min_status outside 0 .. 2; max_object_cells < 0; a weight outside 0 .. 32767; a workspace too small.
+ * ------------------------------------------------------------------------------------------- */
+int crd_plan_rollouts(const double* pose, const double* vw, const double* arc, const double* tau, int32_t M, int32_t n_v, int32_t n_w,
+                      int32_t P, const int64_t* origin, uint64_t cell_f64_bits, const uint8_t* cost, const int32_t* togo, int32_t nx,
+                      int32_t ny, int32_t blocked_at, int32_t outside_blocks, const int32_t* tracks, const double* pos, const double* vel,
+                      int32_t T, int32_t min_status, int32_t max_object_cells, uint64_t min_speed2_f64_bits, uint64_t keep_out2_f64_bits,
+                      const double* twist, uint64_t a_v_dt_f64_bits, uint64_t a_w_dt_f64_bits, int32_t w_togo, int32_t w_max_cost,
+                      int32_t w_sum_cost, int32_t w_slow, int32_t w_turn, void* workspace, int64_t workspace_bytes, int32_t* best,
+                      double* command, int64_t* score, int32_t* info, int64_t* scores, int32_t* first_blocked, int32_t* first_track,
+                      int32_t* max_cost, int32_t* end_togo, double* xy, crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Visualisation back end: float maps, label maps and the radar channel -> uint8 RGB pictures ("Visualisation back
  * end"; the reference's src/visualization/visualization.py:102-151 without its PNG files).  No allocation, no synchronisation,
  * capturable in a graph on one stream, arguments checked before any GPU call.  The three entries add no struct and change no
