@@ -10,11 +10,11 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcamradepth_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-inline-asm"]
 # Per-file flags.  -fno-slp-vectorize: the SLP vectoriser pairs the per-channel fp32 loops of the elementwise / stencil kernels into
-# v_pk_fma_f32 and keeps every unpacked operand alive to do so (k_bicubic_bwd_tile: 452 instead of 106 registers, k_bicubic 194 -> 124,
-# k_dwconv_wgrad 354 -> 255: two workgroups per CU instead of one; attention.hip was part of encoder_ops.hip when that was decided and
-# keeps the flag its kernels were tuned with); norm.hip measured 0.17 ms per step SLOWER without it, the MFMA
-# kernels are left as they were (conv3x3.hip gets scratch without it).
-NO_SLP = set((os.environ.get("CRD_NOSLP_FILES") or "decoder_ops,encoder_ops,attention").split(","))
+# v_pk_fma_f32 and keeps every unpacked operand alive to do so (the LDS-tiled bicubic transpose of rounds 5-6: 452 instead of 106
+# registers, its forward 194 -> 124; k_dwconv_wgrad 354 -> 255: two workgroups per CU instead of one; attention.hip was part of
+# encoder_ops.hip and bicubic.hip of decoder_ops.hip when that was decided and keep the flag: bicubic.hip packs its transpose's FMAs by
+# hand); norm.hip measured 0.17 ms per step SLOWER without it, the MFMA kernels are left as they were (conv3x3.hip gets scratch without it).
+NO_SLP = set((os.environ.get("CRD_NOSLP_FILES") or "decoder_ops,encoder_ops,attention,bicubic").split(","))
 EXTRA = (os.environ.get("CRD_EXTRA_FLAGS") or "").split()      # developer switch: e.g. -DCRD_DWW_WGS=1 for an A/B build
 
 

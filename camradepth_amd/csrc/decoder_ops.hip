@@ -1,159 +1,10 @@
-// Decoder-side streaming kernels for gfx950: bicubic x2 (forward / transpose), layout conversion at
-// the module boundary, Seg_Block argmax, slice copies and small elementwise helpers.
+// Decoder-side streaming kernels for gfx950: layout conversion at the module boundary, Seg_Block argmax, the depth head's
+// stencils, slice copies and small elementwise helpers.  (Bicubic x2 and its transpose: bicubic.hip.)
 #include "common.h"
 
 namespace {
 
 constexpr int TPB = 256;
-// PyTorch upsample_bicubic2d, A = -0.75, scale 2, align_corners=False:
-// odd output o=2k+1 reads inputs k-1..k+2 with WO, even output o=2k reads k-2..k+1 with WE.
-__device__ __constant__ float WO[4] = {-0.10546875f, 0.87890625f, 0.26171875f, -0.03515625f};
-__device__ __constant__ float WE[4] = {-0.03515625f, 0.26171875f, 0.87890625f, -0.10546875f};
-
-__device__ __forceinline__ void taps_of(int o, int n, int (&idx)[4], float (&w)[4]) {
-  const int k = o >> 1;
-  const bool odd = o & 1;
-  const int base = odd ? k - 1 : k - 2;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    int i = base + t;
-    idx[t] = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-    w[t] = odd ? WO[t] : WE[t];
-  }
-}
-
-// One thread produces the 2 x 2 outputs above input pixel (k, m) for 8 channels: they share the clamped 5 x 5 input
-// neighbourhood (25 loads instead of 4 x 16), horizontal pass first (even / odd column results of the five rows), then
-// the vertical one -- the same order of operations as the one-output-per-thread form it replaces.
-// F8 = 1: the output is the e4m3 copy (y = bytes, y_ld in bytes) of the bf16 result, scaled by inv_scale; 2: that and the
-// bf16 result itself (y2)
-template <int F8>
-__global__ __launch_bounds__(TPB) void k_bicubic(const bf16_t* x, int x_ld, int H, int W, int C, void* y, int y_ld, float inv_scale,
-                                                 void* y2, int y2_ld) {
-  const int b = blockIdx.y;
-  const int CG = C >> 3;
-  const int OW = 2 * W;
-  const long long total = (long long)H * W * CG;
-  const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-  if (i >= total) return;
-  const int cg = (int)(i % CG);
-  const int pix = (int)(i / CG);
-  const int k = pix / W, m = pix - k * W;
-  const bf16_t* xb = x + (long long)b * H * W * x_ld + cg * 8;
-  int cx[5];
-#pragma unroll
-  for (int c = 0; c < 5; ++c) { const int ix = m - 2 + c; cx[c] = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix); }
-  float he[5][8], ho[5][8];
-#pragma unroll
-  for (int r = 0; r < 5; ++r) {
-    int iy = k - 2 + r;
-    iy = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy);
-    float v[5][8];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) load8(xb, ((long long)iy * W + cx[c]) * x_ld, 0, v[c]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { he[r][j] = 0.f; ho[r][j] = 0.f; }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { he[r][j] += WE[t] * v[t][j]; ho[r][j] += WO[t] * v[t + 1][j]; }
-  }
-#pragma unroll
-  for (int oy = 0; oy < 2; ++oy)
-#pragma unroll
-    for (int ox = 0; ox < 2; ++ox) {
-      float out[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) out[j] = 0.f;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float wy = oy ? WO[t] : WE[t];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) out[j] += wy * (ox ? ho[t + oy][j] : he[t + oy][j]);
-      }
-      const long long opix = (long long)b * 2 * H * OW + (long long)(2 * k + oy) * OW + 2 * m + ox;
-      if (F8) store8_fp8(y, opix * y_ld + cg * 8, out, inv_scale);
-      else store8_bf16(y, opix * y_ld + cg * 8, out);
-      if (F8 == 2) store8_bf16(y2, opix * y2_ld + cg * 8, out);
-    }
-}
-
-// transpose: dx[iy][ix] (+)= sum_{oy,ox} By[oy][iy]*Bx[ox][ix]*dy[oy][ox]; candidates o in [2i-4, 2i+5]
-__device__ __forceinline__ void bwd_weights(int i, int n, float (&w)[10]) {
-#pragma unroll
-  for (int k = 0; k < 10; ++k) {
-    const int o = 2 * i - 4 + k;
-    float acc = 0.f;
-    if (o >= 0 && o < 2 * n) {
-      int idx[4];
-      float ww[4];
-      taps_of(o, n, idx, ww);
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (idx[t] == i) acc += ww[t];
-    }
-    w[k] = acc;
-  }
-}
-
-__global__ __launch_bounds__(TPB) void k_bicubic_bwd(const bf16_t* dy, int dy_ld, int H, int W, int C, bf16_t* dx, int dx_ld,
-                                                     int accumulate) {
-  const int b = blockIdx.y;
-  const int CG = C >> 3;
-  const int OH = 2 * H, OW = 2 * W;
-  const long long total = (long long)H * W * CG;
-  const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-  if (i >= total) return;
-  const int cg = (int)(i % CG);
-  const int pix = (int)(i / CG);
-  const int iy = pix / W, ix = pix - iy * W;
-  float wy[10], wx[10];
-  bwd_weights(iy, H, wy);
-  bwd_weights(ix, W, wx);
-  const bf16_t* db = dy + (long long)b * OH * OW * dy_ld + cg * 8;
-  float out[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) out[j] = 0.f;
-  // border pixels collect clamped taps from further away: widen the window there
-  const bool border = iy < 2 || iy > H - 3 || ix < 2 || ix > W - 3;
-  if (!border) {
-#pragma unroll
-    for (int a = 1; a < 9; ++a) {
-      const int oy = 2 * iy - 4 + a;
-#pragma unroll
-      for (int c = 1; c < 9; ++c) {
-        const int ox = 2 * ix - 4 + c;
-        float v[8];
-        load8(db, ((long long)oy * OW + ox) * dy_ld, 0, v);
-        const float w = wy[a] * wx[c];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) out[j] += w * v[j];
-      }
-    }
-  } else {
-    for (int a = 0; a < 10; ++a) {
-      const int oy = 2 * iy - 4 + a;
-      if (oy < 0 || oy >= OH || wy[a] == 0.f) continue;
-      for (int c = 0; c < 10; ++c) {
-        const int ox = 2 * ix - 4 + c;
-        if (ox < 0 || ox >= OW || wx[c] == 0.f) continue;
-        float v[8];
-        load8(db, ((long long)oy * OW + ox) * dy_ld, 0, v);
-        const float w = wy[a] * wx[c];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) out[j] += w * v[j];
-      }
-    }
-  }
-  const long long off = ((long long)b * H * W + pix) * dx_ld + cg * 8;
-  if (accumulate) {
-    float o[8];
-    load8(dx, off, 0, o);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] += o[j];
-  }
-  store8_bf16(dx, off, out);
-}
 
 __global__ __launch_bounds__(TPB) void k_nchw_to_pm(const float* x, int C, long long HW, bf16_t* y, int y_ld, int Cpad) {
   const int b = blockIdx.y;
@@ -443,107 +294,6 @@ __global__ __launch_bounds__(TPB) void k_head2_wgrad(const float* gd, const bf16
   if (threadIdx.x == 0) grad_add(&dst[288], sm[288]);
 }
 
-// LDS-tiled form of k_bicubic_bwd: a workgroup owns an 8 x 16 tile of input pixels and a 16-channel window (32 channels: 60 KB
-// of LDS, two workgroups per CU, 206 instead of 168 us on the 256 x 416 level); the (2*8+8) x (2*16+8) region of dy that feeds it
-// is loaded once (coalesced, all loads in flight).  The gather kernel above fetched each dy element ~16 times through L1/L2 and
-// 7 times from HBM (rocprofv3 FETCH_SIZE: 421 MB per launch for 233 MB of dy).
-constexpr int BTH = 8, BTW = 16, BCG = 2;                 // tile rows / columns, granules per window
-constexpr int BRH = 2 * BTH + 8, BRW = 2 * BTW + 8;       // dy region
-__global__ __launch_bounds__(TPB) void k_bicubic_bwd_tile(const bf16_t* dy, int dy_ld, int H, int W, int C, bf16_t* dx, int dx_ld,
-                                                          int accumulate, int tiles_x) {
-  __shared__ __attribute__((aligned(16))) uint4 sdy[BRH * BRW * BCG];        // 30 KB: five workgroups per CU
-  const int b = blockIdx.z;
-  const int g0 = blockIdx.y * BCG;                          // first granule of the window
-  const int CG = C >> 3;
-  const int tyi = blockIdx.x / tiles_x, txi = blockIdx.x - tyi * tiles_x;
-  const int y0 = tyi * BTH, x0 = txi * BTW;
-  const int OH = 2 * H, OW = 2 * W;
-  const bf16_t* db = dy + (long long)b * OH * OW * dy_ld;
-  const int t = threadIdx.x;
-  const int g = t & (BCG - 1), xc = (t >> 1) & (BTW - 1), rgp = t >> 5;      // 2 granules x 16 columns x 8 rows
-  const int ix = x0 + xc, iy = y0 + rgp;
-  const bool colok = g0 + g < CG && ix < W;
-  // the tap weights first, pinned in registers (left to the scheduler, the branchy weight code ended up interleaved with the passes)
-  float wx[10], wy[10];
-  bwd_weights(ix < W ? ix : W - 1, W, wx);
-  bwd_weights(iy < H ? iy : H - 1, H, wy);
-#pragma unroll
-  for (int i = 0; i < 10; ++i) asm volatile("" : "+v"(wx[i]), "+v"(wy[i]));
-  {
-    constexpr int NP = (BRH * BRW * BCG + TPB - 1) / TPB;
-    uint4 r[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = t + k * TPB;
-      const int px = i / BCG, gg = i - px * BCG;
-      const int ry = px / BRW, rx = px - ry * BRW;
-      const int oy = 2 * y0 - 4 + ry, ox = 2 * x0 - 4 + rx;
-      // (unconditional loads from a clamped address + select: no early wait behind the first piece)
-      const bool ok = i < BRH * BRW * BCG && g0 + gg < CG && (unsigned)oy < (unsigned)OH && (unsigned)ox < (unsigned)OW;
-      const int cy = oy < 0 ? 0 : (oy < OH ? oy : OH - 1), cx = ox < 0 ? 0 : (ox < OW ? ox : OW - 1), cgr = g0 + gg < CG ? g0 + gg : g0;
-      const uint4 u = *reinterpret_cast<const uint4*>(db + ((long long)cy * OW + cx) * dy_ld + cgr * 8);
-      r[k] = ok ? u : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = t + k * TPB;
-      if (i < BRH * BRW * BCG) sdy[i] = r[k];
-    }
-  }
-  __syncthreads();
-  // The transposed stencil is separable -- dx = By^T (dy Bx) -- and is evaluated that way: a horizontal pass over the region's 24
-  // rows (10 taps each, results kept in registers), then, with the fp32 row sums written back over the dy tile in LDS, a vertical
-  // pass (10 taps).  The dense 10 x 10 form did 100 LDS reads + ~1700 vector operations per (pixel, granule): 276 us on the
-  // 256 x 416 level against ~85 us of memory time.  (Compiled with -fno-slp-vectorize, build.py: the SLP vectoriser pairs the
-  // per-channel FMAs and keeps every unpacked operand alive for it -- 452 registers instead of ~100.)
-  constexpr int RPT = BRH / 8;                                               // region rows per thread in the horizontal pass: 3
-  float hs[RPT][8];
-#pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int ry = k * 8 + rgp;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) hs[k][j] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 10; ++c) {
-      const uint4 u = sdy[(ry * BRW + 2 * xc + c) * BCG + g];
-      const float w = wx[c];
-      hs[k][0] += w * bf_lo(u.x); hs[k][1] += w * bf_hi(u.x); hs[k][2] += w * bf_lo(u.y); hs[k][3] += w * bf_hi(u.y);
-      hs[k][4] += w * bf_lo(u.z); hs[k][5] += w * bf_hi(u.z); hs[k][6] += w * bf_lo(u.w); hs[k][7] += w * bf_hi(u.w);
-    }
-  }
-  __syncthreads();                                                           // every read of the dy tile is done
-  float4* srow = reinterpret_cast<float4*>(sdy);                             // [2 halves][BRH][BTW][BCG] float4: 24 KB of the tile's 30
-  constexpr int HALF = BRH * BTW * BCG;
-#pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int ry = k * 8 + rgp;
-    float4* p = srow + (ry * BTW + xc) * BCG + g;
-    p[0] = make_float4(hs[k][0], hs[k][1], hs[k][2], hs[k][3]);
-    p[HALF] = make_float4(hs[k][4], hs[k][5], hs[k][6], hs[k][7]);
-  }
-  __syncthreads();
-  if (!colok || iy >= H) return;
-  float out[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) out[j] = 0.f;
-#pragma unroll
-  for (int a = 0; a < 10; ++a) {
-    const float4* p = srow + ((2 * rgp + a) * BTW + xc) * BCG + g;
-    const float4 lo = p[0], hi = p[HALF];
-    const float w = wy[a];
-    out[0] += w * lo.x; out[1] += w * lo.y; out[2] += w * lo.z; out[3] += w * lo.w;
-    out[4] += w * hi.x; out[5] += w * hi.y; out[6] += w * hi.z; out[7] += w * hi.w;
-  }
-  const long long off = ((long long)b * H * W + (long long)iy * W + ix) * dx_ld + (g0 + g) * 8;
-  if (accumulate) {
-    float o[8];
-    load8(dx, off, 0, o);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] += o[j];
-  }
-  store8_bf16(dx, off, out);
-}
-
 // workgroups per sample of the head stencil kernels: 4 lanes per pixel, ~8+ pixels per thread on large grids
 inline int head2_blocks(int H, int W, int B) {
   long long n = cdiv(4ll * H * W, TPB);
@@ -553,55 +303,6 @@ inline int head2_blocks(int H, int W, int B) {
 }
 
 }  // namespace
-
-extern "C" int crd_bicubic2x(const void* x, int32_t x_ld, int32_t x_coff, int32_t B, int32_t H, int32_t W, int32_t C, void* y,
-                             int32_t y_ld, int32_t y_coff, crd_stream_t stream) {
-  CRD_CHECK_ARG(x && y, "crd_bicubic2x: null pointer");
-  CRD_CHECK_ARG(C % 8 == 0 && x_ld % 8 == 0 && x_coff % 8 == 0 && y_ld % 8 == 0 && y_coff % 8 == 0, "crd_bicubic2x: alignment");
-  const long long total = 4ll * H * W * (C / 8);
-  hipLaunchKernelGGL(k_bicubic<0>, dim3((unsigned)cdiv(total / 4, TPB), B), dim3(TPB), 0, as_stream(stream),
-                     reinterpret_cast<const bf16_t*>(x) + x_coff, x_ld, H, W, C, reinterpret_cast<bf16_t*>(y) + y_coff, y_ld, 1.f, nullptr, 0);
-  CRD_LAUNCH_CHECK("crd_bicubic2x");
-  return CRD_OK;
-}
-
-extern "C" int crd_bicubic2x_fp8(const void* x, int32_t x_ld, int32_t x_coff, int32_t B, int32_t H, int32_t W, int32_t C, void* y_fp8,
-                                 int32_t y_ld, int32_t y_coff, float y_scale, void* y_bf16, int32_t yb_ld, int32_t yb_coff,
-                                 crd_stream_t stream) {
-  CRD_CHECK_ARG(x && y_fp8 && y_scale > 0.f, "crd_bicubic2x_fp8: null pointer / bad scale");
-  CRD_CHECK_ARG(C % 8 == 0 && x_ld % 8 == 0 && x_coff % 8 == 0 && y_ld % 8 == 0 && y_coff % 8 == 0 && yb_ld % 8 == 0 && yb_coff % 8 == 0,
-                "crd_bicubic2x_fp8: alignment");
-  const long long total = 4ll * H * W * (C / 8);
-  const dim3 grid((unsigned)cdiv(total / 4, TPB), B);
-  if (y_bf16)
-    hipLaunchKernelGGL(k_bicubic<2>, grid, dim3(TPB), 0, as_stream(stream), reinterpret_cast<const bf16_t*>(x) + x_coff, x_ld, H, W, C,
-                       reinterpret_cast<unsigned char*>(y_fp8) + y_coff, y_ld, 1.f / y_scale, reinterpret_cast<bf16_t*>(y_bf16) + yb_coff, yb_ld);
-  else
-    hipLaunchKernelGGL(k_bicubic<1>, grid, dim3(TPB), 0, as_stream(stream), reinterpret_cast<const bf16_t*>(x) + x_coff, x_ld, H, W, C,
-                       reinterpret_cast<unsigned char*>(y_fp8) + y_coff, y_ld, 1.f / y_scale, nullptr, 0);
-  CRD_LAUNCH_CHECK("crd_bicubic2x_fp8");
-  return CRD_OK;
-}
-
-extern "C" int crd_bicubic2x_bwd(const void* dy, int32_t dy_ld, int32_t dy_coff, int32_t B, int32_t H, int32_t W, int32_t C,
-                                 void* dx, int32_t dx_ld, int32_t dx_coff, int32_t accumulate, crd_stream_t stream) {
-  CRD_CHECK_ARG(dy && dx, "crd_bicubic2x_bwd: null pointer");
-  CRD_CHECK_ARG(C % 8 == 0 && dy_ld % 8 == 0 && dy_coff % 8 == 0 && dx_ld % 8 == 0 && dx_coff % 8 == 0, "crd_bicubic2x_bwd: alignment");
-  if (H >= BTH && W >= BTW) {      // LDS-tiled kernel; tiny maps keep the gather kernel
-    const int tiles_x = cdiv(W, BTW), tiles_y = cdiv(H, BTH);
-    hipLaunchKernelGGL(k_bicubic_bwd_tile, dim3(tiles_x * tiles_y, cdiv(C / 8, BCG), B), dim3(TPB), 0, as_stream(stream),
-                       reinterpret_cast<const bf16_t*>(dy) + dy_coff, dy_ld, H, W, C, reinterpret_cast<bf16_t*>(dx) + dx_coff, dx_ld,
-                       accumulate, tiles_x);
-    CRD_LAUNCH_CHECK("crd_bicubic2x_bwd");
-    return CRD_OK;
-  }
-  const long long total = (long long)H * W * (C / 8);
-  hipLaunchKernelGGL(k_bicubic_bwd, dim3((unsigned)cdiv(total, TPB), B), dim3(TPB), 0, as_stream(stream),
-                     reinterpret_cast<const bf16_t*>(dy) + dy_coff, dy_ld, H, W, C, reinterpret_cast<bf16_t*>(dx) + dx_coff, dx_ld,
-                     accumulate);
-  CRD_LAUNCH_CHECK("crd_bicubic2x_bwd");
-  return CRD_OK;
-}
 
 extern "C" int crd_nchw_to_pm(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, void* y, int32_t y_ld, int32_t y_coff,
                               int32_t Cpad, crd_stream_t stream) {
