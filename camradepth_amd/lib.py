@@ -159,6 +159,7 @@ _SIGS = {
     "crd_depth_unproject": "piiiiipipiiLLLipppppp", "crd_point_cloud": "piiiiipipiiLLLipppipplpppppp",
     "crd_bev_grid": "ppppiiipiLLLiiLLiiiplppppppp",
     "crd_occupancy_update": "pppiiipipipiiiiLiLLLLiiiiiipppppplpppppp",
+    "crd_terrain_update": "pppiii" "pipipi" "iii" "LLLLL" "iiiil" "ppppppp" "pl" "pppppppppp" "p",
     "crd_distance_field": "piiiiiippplppppp", "crd_field_paths": "pppiipLpppiiiiiippppppp",
     "crd_nav_field": "piiippipLiiipppp", "crd_nav_paths": "ppiipLppiiipppppp",
     "crd_map_objects": "piiiiiiipLplpppppp",

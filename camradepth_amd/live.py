@@ -17,6 +17,7 @@ from . import nav as nv
 from . import objects as obj
 from . import occupancy as occ
 from . import rollout as ro
+from . import terrain as ter
 from . import tracks as trk
 from .bev import GRID_OPTIONS, BevWorkspace, bev_grid, grid_shape, picture
 from .camera import ORDERS, camera_inputs
@@ -44,6 +45,9 @@ TRACK_OPTIONS = trk.SPEC_OPTIONS
 MATCH_OPTIONS = mt.SPEC_OPTIONS
 # the RolloutSpec's own options but cell, which is the map's, tables (the per-candidate tables as well) and xy (the rollouts in the map frame)
 ROLLOUT_OPTIONS = dict({k: v for k, v in ro.SPEC_OPTIONS.items() if k != "cell"}, tables=False, xy=False)
+# the TerrainMap's own options (M, nx, ny and cell are the occupancy map's), picture (True: also terrain.picture over picture_z_range in
+# cmap) and feeds_field (True: the distance field and what follows it read the terrain's state in place of the occupancy map's)
+TERRAIN_OPTIONS = dict(ter.MAP_OPTIONS, picture=False, picture_z_range=(-2.0, 4.0), cmap="jet", feeds_field=False)
 RADAR_ARGS = ("points", "sweep_index", "frame_offsets", "cam1_from_sensor", "cam2_from_sensor", "lags")
 
 
@@ -94,16 +98,26 @@ class LivePipeline:
     the cost-to-go of nav= and the tracks of tracks= when they are there, from the pose the occupancy update read (the matcher's with
     match=; frame 0's when the frames share one map).  It needs field=, whose cell it takes.  With accel= the current (v, w) lives in
     `rollout_twist`, fp64 [M,2] (zeros after construction), which run(twist=) fills.
+    terrain: None, or a dictionary of TERRAIN_OPTIONS: a TerrainMap (`terrain_map`, owned by this object) of the occupancy map's M, nx,
+    ny and cell, fused over the runs from the same cloud, pose (the matcher's with match=), sensor and centre as the occupancy map, so
+    their origins are equal.  It needs occupancy=.  With feeds_field=True the distance field, and with it check_paths, nav_field,
+    plan_paths and plan_rollouts, read the terrain's state where they read the occupancy map's; objects= and tracks= keep reading the
+    occupancy map.  The map is empty after construction; terrain_map.reset() empties it again.
 
     The graph holds, in this order and without a parallel branch: crd_camera_frontend, radar_inputs, crd_assemble_input into the
     plan's input buffer, the network's forward (weights are packed before a replay when they changed, not inside the graph),
-    point_cloud, bev_grid [, bev.picture] [, match.match_scan], occupancy.update [, occupancy.picture] [, objects.map_objects [, tracks.track_objects]], field.distance_field [, field.picture] [,
+    point_cloud, bev_grid [, bev.picture] [, match.match_scan], occupancy.update [, occupancy.picture] [, terrain.update [, terrain.picture]] [, objects.map_objects [, tracks.track_objects]], field.distance_field [, field.picture] [,
     field.check_paths] [, nav.nav_field [, nav.plan_paths]], Visualizer.render [, rollout.plan_rollouts]."""
 
     def __init__(self, model, B, image_size=(900, 1600), downsample_scale=2, y_cutoff=34, max_points=None, max_sweeps=None,
                  frame_channels=3, order_in="rgb", order_out="bgr", max_depth=100.0, min_distance=1.0, min_z=2.0, cloud=None, viz=None,
-                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None, match=None, rollout=None):
+                 bev=None, occupancy=None, field=None, nav=None, objects=None, tracks=None, match=None, rollout=None, terrain=None):
         fn = "LivePipeline"
+        if terrain is not None:
+            if occupancy is None:
+                raise L.CrdError(f"{fn}: terrain= needs occupancy= (the terrain map takes the occupancy map's window, pose and cell)")
+            if not isinstance(terrain, dict) or not set(terrain) <= set(TERRAIN_OPTIONS):
+                raise L.CrdError(f"{fn}: terrain= holds {sorted(TERRAIN_OPTIONS)}, not {terrain!r}")
         if rollout is not None:
             if field is None:
                 raise L.CrdError(f"{fn}: rollout= needs field= (the rollouts are tested on the distance field's costmap)")
@@ -215,6 +229,13 @@ class LivePipeline:
             self.centre = None if centre is None else torch.tensor(centre, dtype=torch.float64, device=dev)
             M = self.occupancy_map.M
             self.occupancy_picture = torch.empty(M, o["nx"], o["ny"], 3, dtype=torch.uint8, device=dev) if o["picture"] else None
+        self.terrain_opts = None if terrain is None else dict(TERRAIN_OPTIONS, **terrain)
+        self.terrain_map = None
+        if self.terrain_opts is not None:
+            o, omap = self.terrain_opts, self.occupancy_map
+            self.terrain_map = ter.TerrainMap(omap.M, omap.nx, omap.ny, omap.cell, device=dev, **{k: o[k] for k in ter.MAP_OPTIONS})
+            self.terrain_ws = ter.TerrainWorkspace(self.terrain_map, B)
+            self.terrain_picture = torch.empty(omap.M, omap.nx, omap.ny, 3, dtype=torch.uint8, device=dev) if o["picture"] else None
         self.match_spec = None
         if match is not None:
             self.match_spec = mt.MatchSpec(device=dev, **dict(MATCH_OPTIONS, **match))
@@ -301,6 +322,9 @@ class LivePipeline:
             if self.occupancy_map is not None:      # the warm-up pass fused a frame of zeros into the map: the first run starts empty
                 self.occupancy_map.reset()
                 self.occupancy_map.status_word.zero_()
+            if self.terrain_map is not None:        # and into the terrain map
+                self.terrain_map.reset()
+                self.terrain_map.status_word.zero_()
             if self.object_tracks is not None:      # and gave its objects tracks
                 self.object_tracks.reset()
         torch.cuda.current_stream().wait_stream(self.stream)
@@ -355,6 +379,16 @@ class LivePipeline:
                 out["occupancy"] = dict(res)
                 if self.occupancy_picture is not None:
                     out["occupancy"]["picture"] = occ.picture(res, self.occupancy_map, self.occupancy_opts["cmap"], out=self.occupancy_picture)
+                grid = res                          # whose state and origin the field and what follows it read
+                if self.terrain_map is not None:
+                    o = self.terrain_opts
+                    land = ter.update(self.terrain_map, out["cloud"], map_from_points=pose, sensor=self.sensor, centre=self.centre,
+                                      workspace=self.terrain_ws, out=self.terrain_ws.out)
+                    out["terrain"] = dict(land)
+                    if self.terrain_picture is not None:
+                        out["terrain"]["picture"] = ter.picture(land, o["picture_z_range"], o["cmap"], out=self.terrain_picture)
+                    if o["feeds_field"]:
+                        grid = land
                 if self.object_spec is not None:
                     out["objects"] = dict(obj.map_objects(self.object_spec, res, res, workspace=self.object_ws))
                     if self.track_spec is not None:
@@ -362,25 +396,25 @@ class LivePipeline:
                                                                workspace=self.track_ws))
                 if self.field_spec is not None:
                     o = self.field_opts
-                    dist = fld.distance_field(self.field_spec, res, workspace=self.field_ws, out=self.field_ws.out)
+                    dist = fld.distance_field(self.field_spec, grid, workspace=self.field_ws, out=self.field_ws.out)
                     out["field"] = dict(dist)
                     if self.field_picture is not None:
                         out["field"]["picture"] = fld.picture(dist, self.field_spec, o["cmap"], out=self.field_picture)
                     if self.paths_xy is not None:
-                        out["field"]["paths"] = dict(fld.check_paths(self.field_spec, dist, res, self.paths_xy, self.path_n_poses, self.path_map,
+                        out["field"]["paths"] = dict(fld.check_paths(self.field_spec, dist, grid, self.paths_xy, self.path_n_poses, self.path_map,
                                                                      blocked_at=o["blocked_at"], outside_blocks=o["outside_blocks"],
                                                                      out=self.paths_out))
                     if self.nav_spec is not None:
-                        field_to_go = nv.nav_field(self.nav_spec, dist, res, self.nav_goals, self.nav_n_goals, workspace=self.nav_ws)
+                        field_to_go = nv.nav_field(self.nav_spec, dist, grid, self.nav_goals, self.nav_n_goals, workspace=self.nav_ws)
                         out["nav"] = dict(field_to_go)
                         if self.nav_starts is not None:
-                            out["nav"]["paths"] = dict(nv.plan_paths(self.nav_spec, field_to_go, res, self.nav_starts, self.nav_P,
+                            out["nav"]["paths"] = dict(nv.plan_paths(self.nav_spec, field_to_go, grid, self.nav_starts, self.nav_P,
                                                                      self.nav_path_map, xy=bool(self.nav_opts["xy"]), out=self.nav_paths_out))
         if self.visualizer is not None:
             out["pictures"] = self.visualizer.render(self.image, p.x_in if self.radar_on else None, pred)
         if self.rollout_spec is not None:
             o, M = self.rollout_opts, self.occupancy_map.M
-            out["rollout"] = dict(ro.plan_rollouts(self.rollout_spec, pose[:M], out["field"], out["occupancy"], nav_result=out.get("nav"),
+            out["rollout"] = dict(ro.plan_rollouts(self.rollout_spec, pose[:M], out["field"], grid, nav_result=out.get("nav"),
                                                    tracks=self.object_tracks, twist=self.rollout_twist, workspace=self.rollout_ws,
                                                    tables=bool(o["tables"]), xy=bool(o["xy"])))
         return out
@@ -414,8 +448,8 @@ class LivePipeline:
         (with rollout=dict(accel=(a_v, a_w)) only); None: that of the run before.
 
         Returns 'image' (uint8 [B,h,w,3]), 'x' (the network input), 'radar' and 'rad_vel' (with radar), 'pred' (the reference's nested
-        output dictionary), 'cloud', 'bev', 'match', 'occupancy', 'objects', 'tracks', 'field', 'nav', 'pictures' and 'rollout' (if asked for at construction: the
-        dictionaries of point_cloud, of bev_grid, of match.match_scan, of occupancy.update, of objects.map_objects, of tracks.track_objects and of field.distance_field -- each with 'picture' if asked for, the last with
+        output dictionary), 'cloud', 'bev', 'match', 'occupancy', 'terrain', 'objects', 'tracks', 'field', 'nav', 'pictures' and 'rollout' (if asked for at construction: the
+        dictionaries of point_cloud, of bev_grid, of match.match_scan, of occupancy.update, of terrain.update, of objects.map_objects, of tracks.track_objects and of field.distance_field -- each with 'picture' if asked for, the last with
         'paths', check_paths' dictionary --, of nav.nav_field -- with 'paths', plan_paths' dictionary --, of Visualizer.render and of rollout.plan_rollouts).  They are VIEWS of this
         object's static buffers, valid until the
         next run(), which overwrites them in place; clone=True returns copies.  Nothing is allocated (with clone=False) and the call

@@ -1003,6 +1003,89 @@ int crd_occupancy_update(const float* xyz, const uint8_t* valid, const int32_t* 
                          int64_t* origin, crd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Terrain map: point clouds -> a ground height per cell, fused over frames in the occupancy map's rolling window, and per cell the
+ * step, the slope and a traversability state from LOCAL height differences ("Terrain map").  A stage beside the
+ * occupancy map, with its conventions: fp64 quantities through device memory or as IEEE-754 bit patterns, no allocation, no
+ * synchronisation, capturable in a graph on one stream, arguments checked before any GPU call.  The entry adds no struct and changes
+ * no signature: CRD_ABI_VERSION stays.  The rows use IEEE fp64 add, multiply, divide, floor and compare, every operation rounded on its
+ * own and every comparison made on the double; everything behind them is integer arithmetic, with floor division (Python's //).
+ * tests/terrain_ref.py restates the entry in NumPy and the kernels agree with it bit for bit; csrc/terrain_cell.h holds the per-cell
+ * rule for the kernels and for a host test.
+ *
+ * The map.  M maps of nx x ny cells of `cell` metres: the window, the torus, prev_origin, cur_origin, initialised and status are
+ * crd_occupancy_update's, word for word, so the same centre and pose give the same origin.  Heights are integers of z_quantum metres
+ * ("quanta").  State of the caller, on the device, per slot [m][wx mod nx][wy mod ny]: map_ground int32, the fused ground height;
+ * map_top int32, the fused highest point under the headroom; map_weight int16, the number of fused observations, 0: never seen.  A
+ * slot of weight 0 holds ground = top = 0.
+ * Numbers the caller makes and passes as integers: head_q = min(floor(headroom / z_quantum), 2^30); step_max_q =
+ * min(max(floor(step_max / z_quantum), 1), 2^30); slope2_max = min(max(floor((2 * cell * slope_max / z_quantum)^2), 1), 2^62), with
+ * slope_max rise over run (a gradient is taken over two cells).  Heights stay below 2^24 quanta in size (z_min, z_max below), so a
+ * step is below 2^25, slope2 below 2^53, and every product here fits int64; the bounds 2^30 and 2^62 change no result.
+ *
+ * Rows: xyz, valid, frame_offsets, rows_per_frame, B, n_rows, map_from_points, t_stride, sensor, sensor_stride, centre, centre_stride,
+ * "T . (x, y, z)", S_b and C_m exactly as for crd_occupancy_update.  M == B: frame b feeds map b; M == 1: every frame feeds map 0.
+ *
+ * Launch 1, prepare.  lo[m][i][j] = INT32_MAX, hi[m][i][j] = INT32_MIN, n[m][i][j] = 0 for every window cell; S_b, status bit 2, the
+ * skip rule (status bit 1) and the origins as launch 1 of crd_occupancy_update.
+ * Launch 2, points A (left out with n_rows == 0).  Row p of frame b, (x, y, z) its floats converted to fp64, m its map:
+ *   1. skipped when valid != NULL and valid[p] == 0, or when it has no frame; (X, Y, Z) = T_b . (x, y, z); skipped unless X, Y, Z and
+ *      the three components of S_b are finite
+ *   2. dx = X - Sx, dy = Y - Sy, r2 = dx * dx + dy * dy; skipped when r2 > max_range * max_range (a point at the sensor stays)
+ *   3. skipped when Z < z_min or Z > z_max
+ *   4. q = (int)floor(Z / z_quantum)
+ *   5. wx = floor(X / cell), wy = floor(Y / cell); skipped unless ox <= wx < ox + nx and oy <= wy < oy + ny, compared as doubles,
+ *      (ox, oy) = cur_origin[m]; with (i, j) = (wx - ox, wy - oy):  lo[m][i][j] = min(lo[m][i][j], q),  n[m][i][j] += 1
+ * Launch 3, points B (left out with n_rows == 0).  Steps 1 to 5 again for every row; where q <= lo[m][i][j] + head_q, compared in
+ * 64-bit integers:  hi[m][i][j] = max(hi[m][i][j], q).  What stands higher than the headroom above the lowest point of its cell is not
+ * in the vehicle's way.  The cell is OBSERVED when n[m][i][j] >= min_points; then lo <= hi.
+ * Launch 4, fuse.  Window cell (m, i, j) is world cell (wx, wy) = (ox + i, oy + j) in slot (wx mod nx, wy mod ny);
+ *   w = the slot's weight if initialised[m] was nonzero before the call and the world cell lies in the prev_origin window, else 0
+ *   (ground, top) = the slot's if w > 0, else (0, 0)
+ *   observed and w == 0:  ground = lo, top = hi
+ *   observed and w > 0:   ground = (w * ground + lo) // (w + 1),  top = (w * top + hi) // (w + 1)        in int64
+ *   observed:             w = min(w + 1, w_max)
+ *   the slot = (ground, top, w) (each slot belongs to exactly one window cell).  top >= ground stays true.
+ *   A skipped map: no slot is written.
+ * Launch 5, derive, from the slots of the current window after launch 4 (a skipped map: the window it had, its slots counting as
+ * weight 0 if initialised[m] was zero).  A neighbour outside the window or of weight 0 is unknown.  For a cell of weight > 0:
+ *   step   = max(top - ground, max over the known ones of the 8 neighbours of |ground_nb - ground|)
+ *   gx     = ground[i+1][j] - ground[i-1][j] when both are known; 2 * (ground[i+1][j] - ground) or 2 * (ground - ground[i-1][j]) when
+ *            one is; else 0.  gy likewise along j.  slope2 = gx * gx + gy * gy in int64
+ *   state  = 2 (occupied) when step > step_max_q or slope2 > slope2_max, else 1 (free)
+ *   hazard = 254 when occupied, else max(step * 253 // step_max_q, slope2 * 253 // slope2_max)
+ *   value  = (float)((double)ground * z_quantum)
+ * and for a cell of weight 0: step = 0, slope2 = 0, state = 0 (unknown), hazard = 255, value = the NaN of bits 0x7fc00000.
+ * initialised[m] = 1 unless the map was skipped.
+ * Outputs in WINDOW order, [M][nx][ny], written in full: ground, top int32 (INT32_MIN where the weight is 0), step int32, slope2
+ * int64, weight int16, state, hazard uint8, evidence uint8 (1 where the cell was observed in this call; 0 all over a skipped map),
+ * value fp32; origin int64 [M][2] = cur_origin after launch 1.
+ *
+ * The same bits every run: only integer minimum, maximum, add and or, whose results do not depend on the order of arrival.  No
+ * workgroup waits for another.  An atomic is skipped where a plain read already settles it; rows of neighbouring lanes of a wave that
+ * fall into one cell are folded first and issue one set of atomics, which changes no result.
+ * workspace, 16-byte aligned, each part from the next multiple of 16 bytes: lo, hi, n int32 [M][nx][ny] each; S fp64 [B][3]; the maps'
+ * flags of this call int32 [M]:
+ *   workspace_bytes >= 3 * ((4 * M * nx * ny + 15) & ~15) + ((24 * B + 15) & ~15) + ((4 * M + 15) & ~15).
+ * CRD_E_INVALID, nothing launched: a NULL workspace, state, output or origin pointer, NULL xyz with n_rows > 0; xyz, frame_offsets,
+ * initialised, status, value, map_ground, map_top, ground, top or step not 4-byte aligned, map_weight or weight not 2-byte,
+ * map_from_points, sensor, centre, slope2 or an origin not 8-byte, the workspace not 16-byte aligned; B <= 0; n_rows < 0; M neither B
+ * nor 1; nx or ny outside 1 .. 65535; M * nx * ny >= 2^31; cell or z_quantum not finite and positive; max_range not positive or its
+ * square not finite; z_min or z_max not finite, z_min > z_max, or |z| / z_quantum >= 2^24 for either; t_stride not 0 or 12;
+ * sensor_stride or centre_stride not 0 or 3; both or neither of frame_offsets and rows_per_frame; min_points < 1; w_max outside
+ * 1 .. 32767; head_q outside 0 .. 2^30 (a negative headroom); step_max_q outside 1 .. 2^30; slope2_max outside 1 .. 2^62; a workspace
+ * too small.
+ * ------------------------------------------------------------------------------------------- */
+int crd_terrain_update(const float* xyz, const uint8_t* valid, const int32_t* frame_offsets, int32_t rows_per_frame, int32_t B,
+                       int32_t n_rows, const double* map_from_points, int32_t t_stride, const double* sensor, int32_t sensor_stride,
+                       const double* centre, int32_t centre_stride, int32_t M, int32_t nx, int32_t ny, uint64_t cell_f64_bits,
+                       uint64_t z_quantum_f64_bits, uint64_t z_min_f64_bits, uint64_t z_max_f64_bits, uint64_t max_range_f64_bits,
+                       int32_t head_q, int32_t min_points, int32_t w_max, int32_t step_max_q, int64_t slope2_max, int32_t* map_ground,
+                       int32_t* map_top, int16_t* map_weight, int64_t* prev_origin, int64_t* cur_origin, int32_t* initialised,
+                       int32_t* status, void* workspace, int64_t workspace_bytes, int32_t* ground, int32_t* top, int32_t* step,
+                       int64_t* slope2, int16_t* weight, uint8_t* state, uint8_t* hazard, uint8_t* evidence, float* value, int64_t* origin,
+                       crd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Distance field: a state map -> per cell the squared distance to the nearest source cell, that cell, the clearance in metres and
  * an inflated costmap; and a check of candidate trajectories against the costmap ("Distance field").  The step after
  * the occupancy map, with its conventions: no allocation, no synchronisation, capturable in a graph on one stream, arguments checked
